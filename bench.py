@@ -26,24 +26,32 @@ the other ranks' records precomputed outside the timed region (what one rank of 
 cfg3 is BASELINE config 3: a stream of 300 frames.  With K + W < 300 the first 300 - K - W frames are fused UNTIMED
 through the same four-stream path, so that the W warm-up and K timed frames are the LAST frames of the 300-frame
 config (a young map has short rays and flatters the number: VERDICT r02); `config.frames_in_map_at_end` = 300.
---map-frames overrides (0 = K + W, the young map).
+--map-frames overrides (0 = K + W, the young map).  One map holds at most MAX_MAP_FRAMES frames (cfg3 300, cfg4 100): larger
+K are timed in passes over the last frames of such a stream, each from an empty map, so that every timed step is a frame of
+the same workload and the pool never outgrows its 30-bit index (frame_plan).
 
-The default single-GPU cfg3 line also carries `other_configs` (round 5): cfg4 through a child run of this script (`--workload cfg4 --lean`),
+A plain run sets up, warms up, times the K-frame windows, writes the outputs of the last timed frame if --dump-outputs DIR is
+given, and prints the line.  Everything else it can measure or check runs only with --full: the sequential per-stage pass,
+the pipeline fill, the frame latency, the corrected-tracker line, the other partition (N > 1), the map and tracker facts at
+the end, `cpu_baseline` and `other_configs`.
+
+With --full the single-GPU cfg3 line also carries `other_configs` (round 5): cfg4 through a child run of this script (`--workload cfg4 --lean`),
 cfg2 and the cfg5 stand-in through tools/mesh_bench.py (stage times from HIP events inside the C calls, algorithmic bytes, fractions, renders),
 and `wall` (seconds in this process's GPU legs, in the children, in the CPU oracle -- which runs LAST).
 
 Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel = whichever of the march kernel and the tracker
 kernel EXECUTES longer (each alone on the GPU in the sequential pass after the timed region: the order of the rocprofv3
 kernel statistics; an event interval on a busy device also contains the launch's wait for its turn, which is most of
-the difference between the tracker's 0.25 ms and the 0.31-0.35 ms between its events).  Its numbers are the LIVE ones:
+the difference between the tracker's 0.25 ms and the 0.31-0.35 ms between its events); without --full there is no such
+pass and the longer live interval decides.  Its numbers are the LIVE ones:
 both kernels are timed with HIP events on their launch streams inside the timed region (svoslam_stage_timing),
 algorithmic bytes per launch (march 4*(levels+steps) + 4*W*H, ICP 48 B per pixel per iteration) over the
 mean interval.  `roofline_stages` carries the same for march, tracker and
-fusion; the fusion's 18 launches are timed in a short SEQUENTIAL pass over three more frames after the timed region
+fusion (--full); the fusion's 18 launches are timed in a short SEQUENTIAL pass over three more frames after the timed region
 (event pairs on the map stream would cost the timed region ~1.5 %).  `traffic` = HBM bytes per frame from the committed
 rocprofv3 PMC passes (profiles/pmc_traffic.json, written by tools/prof/profile_round.sh; counters cannot be sampled
 from inside the process) -- missing entries for the chosen workload are an ERROR, not a null.
-`cpu_baseline` times the single-thread CPU oracle (kind "port") on the TIMED frames of the same stream, continued from the
+`cpu_baseline` (--full) times the single-thread CPU oracle (kind "port") on the TIMED frames of the same stream, continued from the
 GPU's map and pose before them.  `value` is the median of --repeats windows (each from an empty map); `runs` lists them all,
 `pipeline_fill` states the share of the cold five-stream pipeline's fill inside the window.
 """
@@ -71,6 +79,12 @@ WORKLOADS = {
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
 HBM_MEASURED_COPY_GBS = 6290.0  # the same guide's measured copy ceiling; quoted beside the spec peak
 
+
+# Frames one map may hold: config 3's 300-frame stream; 100 frames of config 4 (45 frames hold 337 M nodes, the 30-bit index
+# range ends at 1074 M).  K + W frames beyond it are timed in PASSES of the last frames of such a stream (frame_plan).
+MAX_MAP_FRAMES = {"cfg3": 300, "cfg4": 100}
+# windows after the first run only while all of them fit in this many seconds of wall clock (`--repeats` is an upper bound)
+REPEAT_BUDGET_S = 10.0
 
 LINE_LIMIT = 6000   # bytes: the driver keeps ~8 KB of stdout; round 5's 20.9 KB line was cut and its record lost
 
@@ -188,6 +202,23 @@ def compact_line(full, details_path=None, limit=LINE_LIMIT):
     return line
 
 
+def frame_plan(workload, steps, warmup, map_frames=None):
+    """(total, pre, passes): the stream has `total` frames; `passes` lists the timed frame counts (they sum to `steps`); pass p
+    times frames [total - passes[p], total) after fusing frames [0, total - passes[p]) untimed from an empty map, `pre` of them
+    ahead of the first pass's warm-up.  When steps + warmup fit the map (MAX_MAP_FRAMES, or a larger --map-frames), or the warm-up
+    alone does not, there is ONE pass: the last K frames of a `map_frames`-frame stream (0 = K + W, the young map).  Beyond it every pass but the last times
+    total - W frames, so no map grows past what the pool can index."""
+    mf = map_frames if map_frames is not None else (300 if workload == "cfg3" else 0)
+    cap = max(MAX_MAP_FRAMES[workload], mf)
+    if steps + warmup <= cap or warmup >= cap:
+        pre = max(0, mf - (steps + warmup))
+        return pre + warmup + steps, pre, [steps]
+    total = max(mf or cap, warmup + 1)
+    seg = total - warmup
+    passes = [seg] * (steps // seg) + ([steps % seg] if steps % seg else [])
+    return total, 0, passes
+
+
 def write_details(full, path):
     """the full record (every number of every leg) beside the compact line; a failure to write is reported, never fatal"""
     try:
@@ -261,6 +292,32 @@ def device_memory(P, torch):
             "device_in_use_all_processes": (total_b - free_b) / GiB, "device_total": total_b / GiB}
 
 
+DUMP_NODE_SAMPLE = 1 << 19    # node words written by --dump-outputs: 8 MB + 4 MB of indices; with a 1080p image (33 MB) < 64 MB in all
+
+
+def dump_outputs(out_dir, P, torch):
+    """what the timed path hands its caller after its last frame, as float32 / float64 .npy files in `out_dir`: the ray-cast
+    image (H x W x 4), the tracker's pose (position, column-major orientation) and the map -- its node count and the two words
+    of DUMP_NODE_SAMPLE nodes at fixed, seeded indices (the whole pool is GBs).  uint32 words and indices are exact in float64."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    n = int(P.pool.size)
+    idx = np.unique(np.random.default_rng(20240607).integers(0, n, min(n, DUMP_NODE_SAMPLE))) if n else np.zeros(0, np.int64)
+    words = np.empty((len(idx), 2), np.uint32)
+    if n:
+        class _Words:
+            __cuda_array_interface__ = {"shape": (2 * n,), "typestr": "<i4", "data": (P.pool.data_ptr, False), "version": 2}
+        w = torch.as_tensor(_Words(), device="cuda").view(n, 2)
+        words = w[torch.from_numpy(idx).cuda()].cpu().numpy().view(np.uint32)
+    pos, ori = P.cam.pose()
+    out = {"image": P.image.cpu().numpy().astype(np.float32), "pose_position": np.asarray(pos, np.float32),
+           "pose_orientation": np.asarray(ori, np.float32), "pool_nodes": np.array([n], np.float64),
+           "pool_sample_index": idx.astype(np.float64), "pool_sample_words": words.astype(np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def other_configs(args):
     """the other BASELINE configurations, each in a child process on the same GPU; a failure is IN the record"""
     out = {}
@@ -277,7 +334,8 @@ def other_configs(args):
             return {"error": repr(e)}, time.perf_counter() - t0
 
     me = os.path.abspath(__file__)
-    d, w = child([sys.executable, me, "--workload", "cfg4", "--steps", "40", "--warmup", "5", "--repeats", "3", "--lean", "--full-line", "--cpu-budget", "7", "--cpu-min-frames", "5"]
+    d, w = child([sys.executable, me, "--workload", "cfg4", "--steps", "40", "--warmup", "5", "--repeats", "3", "--full", "--lean", "--full-line", "--cpu-budget", "7",
+                  "--cpu-min-frames", "5"]
                  + (["--no-cpu-baseline"] if args.no_cpu_baseline else []), 300)
     if "error" in d:
         out["cfg4"] = d
@@ -331,8 +389,9 @@ def main():
                     help="frames in the map when the timed region ENDS (default: 300 for cfg3 = BASELINE config 3, K + W for "
                          "cfg4); the frames before the warm-up are fused untimed; 0 = K + W")
     ap.add_argument("--repeats", type=int, default=5,
-                    help="the K-frame window is measured this many times, each from an empty map (reset + history + warm-up + K timed "
-                         "frames); `value` is the median run, `runs` lists them all")
+                    help="the K-frame window is measured up to this many times, each from an empty map (reset + history + warm-up + K timed "
+                         "frames); windows after the first only while all fit in %g s; `value` is the median run, `runs` lists them all"
+                         % REPEAT_BUDGET_S)
     ap.add_argument("--no-other-partition", action="store_true",
                     help="N > 1: do not also measure the other partition (by default the line carries both north_star's row-band "
                          "'allreduce' scheme and the frame-sharded 'deltas' scheme: `value` is --exchange's, `other_partition` the other's)")
@@ -356,7 +415,18 @@ def main():
     ap.add_argument("--stages", action="store_true",
                     help="add `stages` (per-stage durations from HIP-event marks at the stage boundaries, svoslam_runner_timeline); "
                          "the ~10 extra event records per frame cost ~6 %% of the frame rate, so they are off for the headline line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the sequential per-stage pass, the pipeline fill, the frame "
+                         "latency, the corrected-tracker line, the other partition (N > 1), the map / tracker facts at the end, `cpu_baseline` "
+                         "and `other_configs` (each still subject to its --no-* switch); without it the run sets up, warms up, times the "
+                         "windows and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed windows, write what the timed path handed its caller after its last frame as DIR/<name>.npy "
+                         "(float32 / float64): the ray-cast image, the tracker's pose and a fixed, seeded sample of the map's node words")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_other_configs = args.no_corrected_line = args.no_stage_pass = args.no_other_partition = True
+        args.lean = True
 
     t_start = time.perf_counter()
     wall = {}
@@ -438,9 +508,7 @@ def main():
 
     width, height, max_depth, center, edge = WORKLOADS[args.workload]
     K, Wm = args.steps, args.warmup
-    map_frames = args.map_frames if args.map_frames is not None else (300 if args.workload == "cfg3" else 0)
-    pre = max(0, map_frames - (K + Wm))     # fused untimed before the warm-up
-    total = pre + Wm + K
+    total, pre, pass_frames = frame_plan(args.workload, K, Wm, args.map_frames)    # pre: fused untimed before the warm-up
     single = world == 1 and emu is None and not force_dist
     stage_pass = single and not args.no_overlap and not args.no_stage_pass
     extra = 3 if stage_pass else 0          # frames of the sequential per-stage pass after the timed region
@@ -526,9 +594,24 @@ def main():
                 P.run_stream(depth[a:upto], rgb[a:upto], list(range(a, upto)), views[a:upto])
         barrier()
 
-    def timed_window(first, include_h2d=False):
-        """frames [first, total) timed between barrier + synchronize on both sides; the state before it is history(first)"""
+    def timed_window(firsts=None, include_h2d=False):
+        """per pass, frames [first, total) timed between barrier + synchronize on both sides after history(first) (default: the
+        passes of frame_plan, K frames in all); times, counters and stage timings are summed over the passes"""
         P = cur["P"]
+        el, st, lv, march, tracker, marches = 0.0, 0, 0, [0.0, 0], [0.0, 0], 0
+        for first in (firsts if firsts is not None else [total - n for n in pass_frames]):
+            e, s, l, m, tr, n = timed_pass(P, first, include_h2d)
+            el += e; st += s; lv += l; marches += n
+            march[0] += m[0]; march[1] += m[1]; tracker[0] += tr[0]; tracker[1] += tr[1]
+        t = torch.tensor([el], dtype=torch.float64, device="cuda")
+        if world > 1:
+            import torch.distributed as tdist
+            tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
+        runner_ = getattr(P, "_runner", None)
+        return {"timeline": runner_.timeline() if (args.stages and runner_ is not None and not args.no_overlap) else None,
+                "elapsed": float(t.item()), "steps": st, "levels": lv, "march": tuple(march), "tracker": tuple(tracker), "marches": marches}
+
+    def timed_pass(P, first, include_h2d):
         history(first)
         P.counters.zero_()
         barrier()
@@ -559,34 +642,38 @@ def main():
             P.run_stream(depth[first:total], rgb[first:total], list(range(first, total)), views[first:total])
         barrier()
         el = time.perf_counter() - t0
-        t = torch.tensor([el], dtype=torch.float64, device="cuda")
-        if world > 1:
-            import torch.distributed as tdist
-            tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
         st, lv = (int(x) for x in P.counters.cpu().tolist())
-        runner_ = getattr(P, "_runner", None)
-        rec = {"timeline": runner_.timeline() if (args.stages and runner_ is not None and not args.no_overlap) else None,
-               "elapsed": float(t.item()), "steps": st, "levels": lv, "march": pkg.stage_timing_read(pkg.STAGE_MARCH),
-               "tracker": pkg.stage_timing_read(pkg.STAGE_TRACKER),
-               "marches": P.marched_last_call if getattr(P, "frame_sharded", False) else total - first}
+        rec = (el, st, lv, pkg.stage_timing_read(pkg.STAGE_MARCH), pkg.stage_timing_read(pkg.STAGE_TRACKER),
+               P.marched_last_call if getattr(P, "frame_sharded", False) else total - first)
         pkg.stage_timing([])
         return rec
 
-    # The K-frame window is measured R times, each time from an EMPTY map: reset, the 300 - K - W frames of history, the W
+    # The K-frame window is measured up to R times, each time from an EMPTY map: reset, the 300 - K - W frames of history, the W
     # warm-up frames, barrier, K timed frames (the whole stream is ~0.15 s of GPU time).  `value` is the MEDIAN run (VERDICT
-    # r03: the schedule has two steady states and one window is a coin flip); every run is listed in `runs`.
-    t0w = pre + Wm                                # first timed frame
-    R = max(1, args.repeats)
-    runs = [timed_window(t0w, args.include_h2d) for _ in range(R)]
+    # r03: the schedule has two steady states and one window is a coin flip); every run is listed in `runs`.  Windows after the
+    # first run while all of them fit in REPEAT_BUDGET_S (every rank takes the slowest rank's time, so all run alike).
+    t0w = total - pass_frames[0]                       # first timed frame
+    runs, tw0 = [], time.perf_counter()
+    while len(runs) < max(1, args.repeats):
+        runs.append(timed_window(include_h2d=args.include_h2d))
+        spent = torch.tensor([time.perf_counter() - tw0], dtype=torch.float64, device="cuda")
+        if world > 1:
+            import torch.distributed as tdist
+            tdist.all_reduce(spent, op=tdist.ReduceOp.MAX)
+        if float(spent.item()) * (len(runs) + 1) / len(runs) > REPEAT_BUDGET_S:
+            break
+    R = len(runs)
     order = sorted(range(R), key=lambda i: runs[i]["elapsed"])
     med = runs[order[(R - 1) // 2]]               # (an actual run: its kernel timings go with it)
     elapsed = med["elapsed"]
+    if args.dump_outputs and rank == 0:           # before anything else runs on the pipeline: the state the last timed frame left
+        dump_outputs(args.dump_outputs, P, torch)
     # the cold pipeline's fill: the window starts on an idle device (the contract's barrier), so its first frames pay the
     # latency of the five-stream schedule.  T(K) = fill + K x period, measured with a second window over the last K / 2
     # frames of the same stream (same map at the end): period = (T(K) - T(K/2)) / (K - K/2), fill = T(K) - K x period.
     fill = None
-    if R > 1 and K >= 8 and not args.no_overlap and not args.include_h2d and not args.lean:
-        half = sorted(timed_window(t0w + K // 2)["elapsed"] for _ in range(3))[1]
+    if R > 1 and K >= 8 and len(pass_frames) == 1 and not args.no_overlap and not args.include_h2d and not args.lean:
+        half = sorted(timed_window([t0w + K // 2])["elapsed"] for _ in range(3))[1]
         period = (elapsed - half) / (K // 2)
         if period > 0:
             fill = {"pipeline_fill_ms": (elapsed - K * period) * 1e3, "steady_period_ms": period * 1e3,
@@ -626,7 +713,7 @@ def main():
                 "pose_error_deg_end": err_deg, "pose_error_m_end": err_m, "tracking_lost_levels": Pp.cam.tracking_lost_count()}
 
     end_state = None
-    if rank == 0:
+    if rank == 0 and args.full:
         end_state = end_facts(P)
         end_state["tracker"] = ("reference: RGBDCamera::update with every quirk; its rotational Jacobian (Q14, localization_kernels.cu:207-213: not "
                                 "v x n) drifts by degrees per frame on clean data -- pose_error_*_end is against the generator's ground truth after "
@@ -819,7 +906,7 @@ def main():
             pkg.configure(runner_timeline=1)     # (read when the pipeline's runner is created: at its first stream call, inside the window)
             cur["P"] = pl.SlamPipeline(width, height, max_depth, center, edge, render_mode=mode, count_steps=True, strict_reference=strict,
                                        pool_capacity_nodes=pool_cap)
-            timed_window(t0w)
+            timed_window()
             tl = cur["P"]._runner.timeline()
             if len(tl) == K:
                 a = tl[4:-2]
@@ -839,7 +926,7 @@ def main():
         try:
             cur["P"] = pl.SlamPipeline(width, height, max_depth, center, edge, render_mode=mode, count_steps=True, strict_reference=False,
                                        pool_capacity_nodes=pool_cap)
-            r2 = [timed_window(t0w) for _ in range(min(R, 3))]
+            r2 = [timed_window() for _ in range(min(R, 3))]
             e2 = sorted(r["elapsed"] for r in r2)[(len(r2) - 1) // 2]
             m2 = [r for r in r2 if r["elapsed"] == e2][0]
             corrected_line = {"what": "the same %d timed frames with svoslam_camera_set_strict_reference(cam, 0): this build's corrected tracker "
@@ -860,7 +947,7 @@ def main():
             d2 = pl.DistContext(rank, world, force=force_dist, exchange=oex)
             cur["P"] = pl.SlamPipeline(width, height, max_depth, center, edge, render_mode=mode, dist=d2, count_steps=True,
                                        pool_capacity_nodes=pool_cap)
-            r2 = [timed_window(t0w) for _ in range(min(R, 3))]
+            r2 = [timed_window() for _ in range(min(R, 3))]
             e2 = sorted(r["elapsed"] for r in r2)[(len(r2) - 1) // 2]
             other = {"exchange": oex, "value": K / e2, "unit": "frames/s", "ms_per_step": e2 / K * 1e3, "runs": [K / r["elapsed"] for r in r2],
                      "what": ("SURVEY 8e / north_star: image rows in %d bands, ICP sums all-reduced (19 per frame), sorted band key lists all-gathered "
@@ -873,7 +960,11 @@ def main():
         out = {
             "metric": "SLAM frames/sec (fuse+ICP+raycast)", "value": K / elapsed, "unit": "frames/s",
             "n_gpus": world, "steps": K, "warmup": Wm, "ms_per_step": elapsed / K * 1e3,
-            "value_is": "median of %d windows of K = %d timed frames, each from an empty map (reset, %d frames of history, %d of warm-up)" % (R, K, pre, Wm),
+            "value_is": ("median of %d windows of K = %d timed frames, each from an empty map (reset, %d frames of history, %d of warm-up)" % (R, K, pre, Wm)
+                         if len(pass_frames) == 1 else
+                         "median of %d windows of K = %d timed frames, each in %d passes of the last %s frames of a %d-frame stream, every pass "
+                         "from an empty map (reset, the stream's earlier frames untimed, the last %d of them the warm-up)"
+                         % (R, K, len(pass_frames), "/".join(str(n) for n in sorted(set(pass_frames), reverse=True)), total, Wm)),
             "runs": [K / r["elapsed"] for r in runs], "value_min": K / max(r["elapsed"] for r in runs),
             "value_max": K / min(r["elapsed"] for r in runs),
             # the schedule's two steady states: a run more than 7 % under the best one of this process fell into the slow one

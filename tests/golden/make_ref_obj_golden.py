@@ -7,7 +7,9 @@ external/src/objUtil sources where they lie into oracle/_ref/libobjref.so; this 
     oracle's and the product's loaders on every machine), and
   * the reference's objs/*.obj (inputs only present in the build container; pyramid.obj is skipped:
     its faces use index 0, which reads points[-1] in the reference = undefined behaviour),
-and stores sha256 digests of the VBO / TBO float bits plus the bounding box bits.
+and stores sha256 digests of the VBO / TBO float bits plus the bounding box bits; the arrays themselves for the generated
+files go to tests/golden/ref_obj_loader_arrays.npz (keys "<name>/vbo", "/tbo", "/bbox0", "/bbox1"), and the bytes of the
+reference's OBJ files that tests/data/ does not hold to tests/golden/ref_objs.npz.
 
     python tests/golden/make_ref_obj_golden.py
 """
@@ -42,9 +44,12 @@ def main():
     from oracle import oracle as ora
     ora.build_reference_obj_loader()
     out = {"generated": {}, "reference_objs": {}}
+    arrays, objs = {}, {}
     with tempfile.TemporaryDirectory() as d:
         for name, path in sorted(meshgen.write_generated_objs(d).items()):
-            rec = digest(ora.reference_obj_load(path))
+            mesh = ora.reference_obj_load(path)
+            arrays.update({"%s/%s" % (name, k): v for k, v in mesh.items() if v is not None})
+            rec = digest(mesh)
             rec["input_sha256"] = hashlib.sha256(open(path, "rb").read()).hexdigest()
             out["generated"][name] = rec
     for path in sorted(glob.glob("/root/reference/objs/*.obj")):
@@ -54,6 +59,10 @@ def main():
         rec = digest(ora.reference_obj_load(path))
         rec["input_sha256"] = hashlib.sha256(open(path, "rb").read()).hexdigest()
         out["reference_objs"][name] = rec
+        if not os.path.exists(os.path.join(ROOT, "tests", "data", name)):   # the inputs themselves, as packed data fixtures
+            objs[name[:-len(".obj")]] = np.frombuffer(open(path, "rb").read(), np.uint8)
+    np.savez_compressed(os.path.join(HERE, "ref_objs.npz"), **objs)
+    np.savez_compressed(os.path.join(HERE, "ref_obj_loader_arrays.npz"), **arrays)
     with open(os.path.join(HERE, "ref_obj_loader.json"), "w") as fp:
         json.dump(out, fp, indent=1, sort_keys=True)
         fp.write("\n")

@@ -92,11 +92,27 @@ def test_details_file_round_trips(tmp_path):
     assert p and json.load(open(p)) == full
 
 
+def test_frame_plan_times_exactly_the_steps_and_bounds_the_map():
+    """one pass -- the last K frames of the workload's stream, as ever -- while K + W fit the map; beyond it passes of the last
+    frames of a stream no longer than the map may be, whose timed frames add up to K"""
+    b = _bench()
+    assert b.frame_plan("cfg3", 20, 5) == (300, 275, [20])
+    assert b.frame_plan("cfg3", 295, 5) == (300, 0, [295])
+    assert b.frame_plan("cfg3", 100, 5, 0) == (105, 0, [100])
+    assert b.frame_plan("cfg4", 40, 5) == (45, 0, [40])
+    assert b.frame_plan("cfg3", 100, 5, 400) == (400, 295, [100])
+    for wl, cap in b.MAX_MAP_FRAMES.items():
+        for k, w in ((cap, 5), (cap + 1, 0), (2000, 5), (22222, 5), (5000, 1)):
+            total, pre, passes = b.frame_plan(wl, k, w)
+            assert sum(passes) == k and total <= cap and pre == 0 and len(passes) > 1
+            assert all(0 < n <= total - w for n in passes)
+
+
 @pytest.mark.gpu
 def test_real_bench_output_is_one_short_parseable_line(tmp_path):
     det = str(tmp_path / "details.json")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--cpu-budget", "1",
-                        "--repeats", "2", "--no-other-configs", "--details", det], capture_output=True, text=True, timeout=900)
+                        "--repeats", "2", "--full", "--no-other-configs", "--details", det], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines[:3]
@@ -106,3 +122,48 @@ def test_real_bench_output_is_one_short_parseable_line(tmp_path):
     _check(lines[0], full, 6000)
     assert d["roofline"]["frac"] > 0 and d["cpu_baseline"]["value"] > 0
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_same_outputs_twice(tmp_path):
+    """a plain run (no --full) times exactly --steps frames and, with --dump-outputs, writes the last timed frame's image, pose and
+    map sample as float32 / float64 .npy files (< 64 MB); two runs with the same arguments write identical arrays"""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("out%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--repeats", "1",
+                            "--map-frames", "0", "--details", "", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines[:3]
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+        assert abs(line["value"] * line["ms_per_step"] - 1e3) <= 1e-2 * 1e3
+        assert line["cpu_baseline"] is None and "other_configs" not in line
+        files = sorted(p.name for p in d.iterdir())
+        assert files == ["image.npy", "pool_nodes.npy", "pool_sample_index.npy", "pool_sample_words.npy", "pose_orientation.npy",
+                         "pose_position.npy"], files
+        assert sum(p.stat().st_size for p in d.iterdir()) <= 64 << 20
+        arrs = {f[:-4]: np.load(str(d / f)) for f in files}
+        for a in arrs.values():
+            assert a.dtype in (np.float32, np.float64)
+        assert arrs["image"].shape == (480, 640, 4)
+        assert arrs["pool_nodes"][0] > 0 and arrs["pool_sample_words"].shape == (len(arrs["pool_sample_index"]), 2)
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+
+
+@pytest.mark.gpu
+def test_plain_run_with_more_steps_than_one_map_holds(tmp_path):
+    """--steps beyond the frames one map may hold: the steps are timed in passes, all of them counted"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "700", "--warmup", "5", "--repeats", "2",
+                        "--details", ""], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines[:3]
+    line = json.loads(lines[0])
+    assert line["steps"] == 700 and line["warmup"] == 5 and line["ms_per_step"] > 0
+    assert abs(line["value"] * line["ms_per_step"] - 1e3) <= 1e-2 * 1e3
+    assert line["config"]["frames_in_map_at_end"] == 300 and len(line["runs"]) == 2

@@ -195,6 +195,8 @@ def _two_process_worker(rank, world, port, out_dir, n, w, h, depth, exchange="de
     dstack, cstack = synth.render_stream(n, w, h, device="cuda")
     views = [pl.ground_truth_view(k, synth) for k in range(n)]
     P = pl.SlamPipeline(w, h, depth, center, edge, dist=pl.DistContext(rank, world, exchange=exchange), pool_capacity_nodes=1 << 21)
+    if P.dist.mailbox is not None:   # two processes time-sliced on one shared device: a wait may take seconds, not the default ~1 s
+        P.dist.mailbox.set_wait_limit(1 << 28)
     imgs = [torch.zeros((h, w, 4), dtype=torch.uint8, device="cuda") for _ in range(n)]
     half = n // 2 + 1
     P.run_stream_sharded(list(dstack[:half]), list(cstack[:half]), list(range(half)), views[:half], images=imgs[:half], per_rank=2)
@@ -259,7 +261,7 @@ def test_bench_multi_rank_code_path_on_one_gpu(env):
         envv = dict(os.environ, SVOSLAM_BENCH_ONE_DEVICE="1")
         out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc),
                               "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                              "--gpus", str(nproc), "--steps", "12", "--warmup", "3", "--map-frames", "0", "--no-cpu-baseline"],
+                              "--gpus", str(nproc), "--steps", "12", "--warmup", "3", "--map-frames", "0", "--full", "--no-cpu-baseline"],
                              env=envv, capture_output=True, text=True, timeout=600)
         lines = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]
         assert out.returncode == 0 and len(lines) == 1, (out.returncode, out.stdout[-800:], out.stderr[-1500:])

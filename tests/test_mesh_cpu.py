@@ -3,11 +3,9 @@ oracle's restatement, and oracle sanity against SURVEY.md Appendix D.8."""
 import os
 
 import numpy as np
-import pytest
 
 import meshgen
-
-REF_OBJS = "/root/reference/objs"
+from util import reference_obj
 
 
 def load_pkg():
@@ -40,15 +38,12 @@ def test_obj_loaders_agree(tmp_path, oracle):
     check_same_mesh(pkg, oracle, meshgen.write_soup_obj(tmp_path / "soup.obj"))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_OBJS), reason="reference data files only exist in the build container")
-def test_obj_loaders_on_reference_data(oracle):
+def test_obj_loaders_on_reference_data(tmp_path, oracle):
     pkg = load_pkg()
     # (objs/pyramid.obj is excluded: its double-space separated, 0-based faces make the reference's loader
     #  index points[-1]: undefined behaviour, nothing to agree on)
     for name in ("cube.obj", "bunny_tex.obj", "suzanne.obj"):
-        p = os.path.join(REF_OBJS, name)
-        if os.path.exists(p):
-            check_same_mesh(pkg, oracle, p)
+        check_same_mesh(pkg, oracle, reference_obj(name, tmp_path))
 
 
 def test_bmp_loaders_agree(tmp_path, oracle):

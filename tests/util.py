@@ -52,3 +52,18 @@ def surface_cloud(rng, n, jitter=0.01):
     pts += rng.normal(scale=jitter, size=pts.shape)
     col = rng.integers(0, 256, (n, 3), dtype=np.uint8)
     return pts.astype(np.float32), col
+
+
+def reference_obj(name, out_dir):
+    """path of the reference's objs/<name> (data fixtures: tests/data/, or packed in tests/golden/ref_objs.npz as the
+    file's bytes, unpacked into out_dir)"""
+    import os
+    here = os.path.dirname(os.path.abspath(__file__))
+    path = os.path.join(here, "data", name)
+    if os.path.exists(path):
+        return path
+    packed = np.load(os.path.join(here, "golden", "ref_objs.npz"))
+    path = os.path.join(str(out_dir), name)
+    with open(path, "wb") as fp:
+        fp.write(packed[name[:-len(".obj")]].tobytes())
+    return path

@@ -20,7 +20,7 @@ fail() { echo "FAILED: $*"; FAILED=1; }
 
 echo "== PMC FETCH_SIZE / WRITE_SIZE per kernel (separate passes)"
 PM=${P}_pmc_fetch_write_per_kernel.txt
-echo "# rocprofv3 --pmc <counter> --kernel-include-regex svoslam --kernel-trace -- python bench.py --workload W --no-overlap ... (SVOSLAM_CONFIG=track_mode=1); one counter per pass; KB per dispatch, all dispatches" > $PM
+echo "# rocprofv3 --pmc <counter> --kernel-include-regex svoslam --kernel-trace -- python bench.py --full --workload W --no-overlap ... (SVOSLAM_CONFIG=track_mode=1); one counter per pass; KB per dispatch, all dispatches" > $PM
 declare -A FR TI ARGS
 FR[cfg3]=300; TI[cfg3]=10; ARGS[cfg3]="--steps 10 --warmup 2 --map-frames 300 --repeats 1"
 FR[cfg4]=20;  TI[cfg4]=10; ARGS[cfg4]="--steps 10 --warmup 10 --map-frames 0 --repeats 1"
@@ -29,7 +29,7 @@ for W in cfg3 cfg4; do
   for c in FETCH_SIZE WRITE_SIZE; do
     D=$SCR/pm_${W}_$c; rm -rf $D; mkdir -p $D
     SVOSLAM_CONFIG=track_mode=1 timeout 900 rocprofv3 --pmc $c --kernel-include-regex svoslam --kernel-trace --output-format csv -d $D -o p -- \
-      python $R/bench.py --workload $W ${ARGS[$W]} --no-overlap --no-cpu-baseline --allow-missing-traffic > $SCR/pm_${W}_$c.log 2>&1 || fail "pmc pass $W $c (tail: $(tail -2 $SCR/pm_${W}_$c.log))"
+      python $R/bench.py --full --workload $W ${ARGS[$W]} --no-overlap --no-cpu-baseline --allow-missing-traffic > $SCR/pm_${W}_$c.log 2>&1 || fail "pmc pass $W $c (tail: $(tail -2 $SCR/pm_${W}_$c.log))"
     f=$(find $D -name "*counter_collection.csv" | sort | tail -1)
     [ -n "$f" ] || fail "pmc pass $W $c left no counter_collection.csv"
     cp "$f" $SCR/${W}_$c.csv
@@ -67,20 +67,20 @@ python3 $R/tools/prof/pmc_to_json.py "$OUT/pmc_traffic.json" $TAG $SPECS || fail
 [ $FAILED = 0 ] && cp "$OUT/pmc_traffic.json" $R/profiles/pmc_traffic.json
 
 echo "== bench lines"
-python $R/bench.py 2>/dev/null | line > ${P}_bench_cfg3.json
-python $R/bench.py --steps 20 --warmup 5 2>/dev/null | line > ${P}_bench_cfg3_driver_args_20frames.json
-python $R/bench.py --workload cfg4 --steps 40 --warmup 5 2>/dev/null | line > ${P}_bench_cfg4.json
-python $R/bench.py --steps 100 --warmup 5 --no-cpu-baseline --stages 2>/dev/null | line > ${P}_bench_cfg3_with_stages.json
-python $R/bench.py --workload cfg4 --steps 40 --warmup 5 --no-cpu-baseline --stages 2>/dev/null | line > ${P}_bench_cfg4_with_stages.json
+python $R/bench.py --full 2>/dev/null | line > ${P}_bench_cfg3.json
+python $R/bench.py --full --steps 20 --warmup 5 2>/dev/null | line > ${P}_bench_cfg3_driver_args_20frames.json
+python $R/bench.py --full --workload cfg4 --steps 40 --warmup 5 2>/dev/null | line > ${P}_bench_cfg4.json
+python $R/bench.py --full --steps 100 --warmup 5 --no-cpu-baseline --stages 2>/dev/null | line > ${P}_bench_cfg3_with_stages.json
+python $R/bench.py --full --workload cfg4 --steps 40 --warmup 5 --no-cpu-baseline --stages 2>/dev/null | line > ${P}_bench_cfg4_with_stages.json
 if [ -z "$QUICK" ]; then
-  python $R/bench.py --steps 100 --warmup 5 --map-frames 0 --no-cpu-baseline 2>/dev/null | line > ${P}_bench_cfg3_young_map_105frames.json
-  python $R/bench.py --steps 300 --warmup 0 --no-cpu-baseline 2>/dev/null | line > ${P}_bench_cfg3_all_300_frames_timed.json
-  python $R/bench.py --steps 100 --warmup 5 --no-cpu-baseline --include-h2d 2>/dev/null | line > ${P}_bench_cfg3_include_h2d.json
+  python $R/bench.py --full --steps 100 --warmup 5 --map-frames 0 --no-cpu-baseline 2>/dev/null | line > ${P}_bench_cfg3_young_map_105frames.json
+  python $R/bench.py --full --steps 300 --warmup 0 --no-cpu-baseline 2>/dev/null | line > ${P}_bench_cfg3_all_300_frames_timed.json
+  python $R/bench.py --full --steps 100 --warmup 5 --no-cpu-baseline --include-h2d 2>/dev/null | line > ${P}_bench_cfg3_include_h2d.json
   for e in 0/2 0/4 0/8 3/8; do
-    python $R/bench.py --steps 100 --warmup 5 --no-cpu-baseline --emulate-rank $e 2>/dev/null | line > ${P}_bench_cfg3_emulated_rank_$(echo $e | sed "s#/#_of_#").json
+    python $R/bench.py --full --steps 100 --warmup 5 --no-cpu-baseline --emulate-rank $e 2>/dev/null | line > ${P}_bench_cfg3_emulated_rank_$(echo $e | sed "s#/#_of_#").json
   done
   for e in 0/2 3/8; do
-    python $R/bench.py --workload cfg4 --steps 40 --warmup 5 --no-cpu-baseline --emulate-rank $e 2>/dev/null | line > ${P}_bench_cfg4_emulated_rank_$(echo $e | sed "s#/#_of_#").json
+    python $R/bench.py --full --workload cfg4 --steps 40 --warmup 5 --no-cpu-baseline --emulate-rank $e 2>/dev/null | line > ${P}_bench_cfg4_emulated_rank_$(echo $e | sed "s#/#_of_#").json
   done
 fi
 for f in ${P}_bench_*.json; do python3 - "$f" <<'PY'
@@ -142,9 +142,9 @@ echo "== kernel stats (rocprofv3 --kernel-trace --stats) of the bench"
 for W in cfg3 cfg4; do
   A="--steps 20 --warmup 5 --repeats 1 --no-corrected-line"; [ $W = cfg4 ] && A="--workload cfg4 --steps 40 --warmup 5 --repeats 1 --no-corrected-line"
   D=$SCR/ks_$W; rm -rf $D; mkdir -p $D
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $D -o k -- python $R/bench.py $A --no-cpu-baseline > $SCR/ks_$W.log 2>&1 || fail "kernel stats $W"
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $D -o k -- python $R/bench.py --full $A --no-cpu-baseline > $SCR/ks_$W.log 2>&1 || fail "kernel stats $W"
   f=$(find $D -name "*kernel_stats.csv" | sort | tail -1)
-  { echo "# rocprofv3 --kernel-trace --stats -- python bench.py $A --no-cpu-baseline   (all dispatches of the run: map history + warm-up + timed + the sequential stage pass)"
+  { echo "# rocprofv3 --kernel-trace --stats -- python bench.py --full $A --no-cpu-baseline   (all dispatches of the run: map history + warm-up + timed + the sequential stage pass)"
     echo "# bench line of this profiled run: $(grep '^{"metric"' $SCR/ks_$W.log | tail -1)"
     head -1 $f
     grep -v -E "at::native|rocclr|^\"Name" $f; } > ${P}_bench_${W}_kernel_stats.csv
@@ -169,12 +169,12 @@ done
 
 if [ -z "$QUICK" ]; then
 echo "== A/B records of the round's switches (same box): occupancy bricks, deferred commits, tile order of the brick march"
-SVOSLAM_CONFIG=march_bricks=0 python $R/bench.py --no-cpu-baseline 2>/dev/null | line > ${P}_bench_cfg3_ab_bricks_off.json
-SVOSLAM_CONFIG=runner_deferred=0 python $R/bench.py --no-cpu-baseline 2>/dev/null | line > ${P}_bench_cfg3_ab_inplace_commits.json
-SVOSLAM_CONFIG=march_bricks=0,runner_deferred=0 python $R/bench.py --no-cpu-baseline 2>/dev/null | line > ${P}_bench_cfg3_ab_round2_march_and_schedule.json
-SVOSLAM_CONFIG=march_bricks=0 python $R/bench.py --workload cfg4 --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | line > ${P}_bench_cfg4_ab_bricks_off.json
-SVOSLAM_CONFIG=track_stream=0 python $R/bench.py --workload cfg4 --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | line > ${P}_bench_cfg4_ab_chain_tracker.json
-python $R/bench.py --tracker corrected --no-cpu-baseline 2>/dev/null | line > ${P}_bench_cfg3_corrected_tracker.json
+SVOSLAM_CONFIG=march_bricks=0 python $R/bench.py --full --no-cpu-baseline 2>/dev/null | line > ${P}_bench_cfg3_ab_bricks_off.json
+SVOSLAM_CONFIG=runner_deferred=0 python $R/bench.py --full --no-cpu-baseline 2>/dev/null | line > ${P}_bench_cfg3_ab_inplace_commits.json
+SVOSLAM_CONFIG=march_bricks=0,runner_deferred=0 python $R/bench.py --full --no-cpu-baseline 2>/dev/null | line > ${P}_bench_cfg3_ab_round2_march_and_schedule.json
+SVOSLAM_CONFIG=march_bricks=0 python $R/bench.py --full --workload cfg4 --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | line > ${P}_bench_cfg4_ab_bricks_off.json
+SVOSLAM_CONFIG=track_stream=0 python $R/bench.py --full --workload cfg4 --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | line > ${P}_bench_cfg4_ab_chain_tracker.json
+python $R/bench.py --full --tracker corrected --no-cpu-baseline 2>/dev/null | line > ${P}_bench_cfg3_corrected_tracker.json
 for f in ${P}_bench_cfg3_ab_*.json; do python3 -c "import json,sys,os; d=json.load(open('$f')); print('%-60s %8.1f fps  march %.3f ms' % (os.path.basename('$f'), d['value'], d['roofline_stages'][0]['kernel_ms']))"; done
 echo "== brick march anatomy (diag variant of the library: -DSVO_BRICK_DIAG, built by tools/prof/build_diag_variant.sh)"
 if [ -f $R/octree-slam_amd/_variants/libsvoslam_hip_diag.so ]; then

@@ -5,14 +5,14 @@ O=$R/gpurun_out/r05a; mkdir -p $O
 cd $R
 timeout 900 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.log
 tail -3 $O/pytest_gpu.log
-( time timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err ) 2> $O/bench_driver.time
+( time timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err ) 2> $O/bench_driver.time
 tail -c 600 $O/bench_driver.err
 cat $O/bench_driver.time
 cd /tmp; export TMPDIR=/tmp
 for W in cfg3 cfg4; do
   S=/tmp/ks_$W; rm -rf $S; mkdir -p $S
   A="--steps 10 --warmup 2 --map-frames 300 --repeats 1"; [ $W = cfg4 ] && A="--steps 10 --warmup 10 --map-frames 0 --repeats 1"
-  SVOSLAM_CONFIG=track_mode=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $S -o k -- python $R/bench.py --workload $W $A --no-overlap --no-cpu-baseline --allow-missing-traffic --no-other-configs > $O/ks_$W.log 2>&1
+  SVOSLAM_CONFIG=track_mode=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $S -o k -- python $R/bench.py --full --workload $W $A --no-overlap --no-cpu-baseline --allow-missing-traffic --no-other-configs > $O/ks_$W.log 2>&1
   f=$(find $S -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $O/seq_kernel_stats_$W.csv
 done

@@ -9,9 +9,9 @@ for rep in 1 2; do
 for v in 0 1; do
   echo "== rep $rep pair $v"
   SVO_EXP_PAIR=$v python tools/prof/render_only.py 300 2>&1 | grep -E "standalone" | head -1
-  echo -n "cfg3 100:"; SVO_EXP_PAIR=$v python bench.py --steps 100 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
-  echo -n "cfg3 20: "; SVO_EXP_PAIR=$v python bench.py --steps 20 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
-  echo -n "cfg4 40: "; SVO_EXP_PAIR=$v python bench.py --workload cfg4 --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
+  echo -n "cfg3 100:"; SVO_EXP_PAIR=$v python bench.py --full --steps 100 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
+  echo -n "cfg3 20: "; SVO_EXP_PAIR=$v python bench.py --full --steps 20 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
+  echo -n "cfg4 40: "; SVO_EXP_PAIR=$v python bench.py --full --workload cfg4 --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
 done
 done
 SVO_EXP_PAIR=1 timeout 900 python -m pytest tests/test_gpu_render.py tests/test_gpu_bricks.py -m gpu -x -q 2>&1 | grep -E "passed|failed|error" | tail -3

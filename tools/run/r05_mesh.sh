@@ -7,8 +7,8 @@ cd $R
 timeout 1200 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "rc=$?" >> $O/pytest.log
 tail -4 $O/pytest.log
 for c in cfg2 cfg5; do timeout 300 python tools/mesh_bench.py --config $c > $O/mesh_$c.json 2> $O/mesh_$c.err; done
-timeout 300 python bench.py --workload cfg4 --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --lean 2>$O/cfg4.err | grep '^{"metric"' | tail -1 > $O/cfg4.json
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --lean 2>$O/cfg3.err | grep '^{"metric"' | tail -1 > $O/cfg3.json
+timeout 300 python bench.py --full --workload cfg4 --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --lean 2>$O/cfg4.err | grep '^{"metric"' | tail -1 > $O/cfg4.json
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --lean 2>$O/cfg3.err | grep '^{"metric"' | tail -1 > $O/cfg3.json
 python - <<PY
 import json
 for c in ("cfg2","cfg5"):

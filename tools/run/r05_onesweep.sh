@@ -7,8 +7,8 @@ cd $R
 timeout 600 python -m pytest tests/test_gpu_fusion.py tests/test_gpu_pipeline.py tests/test_gpu_sharded.py -x -q > $O/pytest.log 2>&1; echo "rc=$?" >> $O/pytest.log
 tail -4 $O/pytest.log
 for v in 1 0; do
-  SVOSLAM_CONFIG=sort_onesweep=$v timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --lean 2>$O/cfg3_$v.err | grep '^{"metric"' | tail -1 > $O/cfg3_os$v.json
-  SVOSLAM_CONFIG=sort_onesweep=$v timeout 300 python bench.py --workload cfg4 --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --lean 2>$O/cfg4_$v.err | grep '^{"metric"' | tail -1 > $O/cfg4_os$v.json
+  SVOSLAM_CONFIG=sort_onesweep=$v timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --lean 2>$O/cfg3_$v.err | grep '^{"metric"' | tail -1 > $O/cfg3_os$v.json
+  SVOSLAM_CONFIG=sort_onesweep=$v timeout 300 python bench.py --full --workload cfg4 --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --lean 2>$O/cfg4_$v.err | grep '^{"metric"' | tail -1 > $O/cfg4_os$v.json
 done
 python - <<PY
 import json

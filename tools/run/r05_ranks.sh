@@ -4,11 +4,11 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/r05d; mkdir -p $O
 cd $R
 L() { grep '^{"metric"' | tail -1; }
-timeout 300 python bench.py --steps 100 --warmup 5 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | L > $O/cfg3_single.json
-timeout 300 python bench.py --workload cfg4 --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --lean 2>/dev/null | L > $O/cfg4_single.json
+timeout 300 python bench.py --full --steps 100 --warmup 5 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | L > $O/cfg3_single.json
+timeout 300 python bench.py --full --workload cfg4 --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --lean 2>/dev/null | L > $O/cfg4_single.json
 for ss in 0 1; do for g in 0 1; do
-  SVOSLAM_SHARD_SORT=$ss SVOSLAM_CONFIG=graphs=$g timeout 300 python bench.py --steps 100 --warmup 5 --no-cpu-baseline --emulate-rank 3/8 2>$O/e3.err | L > $O/cfg3_rank3of8_sort${ss}_graphs$g.json
-  SVOSLAM_SHARD_SORT=$ss SVOSLAM_CONFIG=graphs=$g timeout 300 python bench.py --workload cfg4 --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --emulate-rank 3/8 2>$O/e4.err | L > $O/cfg4_rank3of8_sort${ss}_graphs$g.json
+  SVOSLAM_SHARD_SORT=$ss SVOSLAM_CONFIG=graphs=$g timeout 300 python bench.py --full --steps 100 --warmup 5 --no-cpu-baseline --emulate-rank 3/8 2>$O/e3.err | L > $O/cfg3_rank3of8_sort${ss}_graphs$g.json
+  SVOSLAM_SHARD_SORT=$ss SVOSLAM_CONFIG=graphs=$g timeout 300 python bench.py --full --workload cfg4 --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --emulate-rank 3/8 2>$O/e4.err | L > $O/cfg4_rank3of8_sort${ss}_graphs$g.json
 done; done
 python - <<PY
 import json, glob, os

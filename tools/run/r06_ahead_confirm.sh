@@ -12,8 +12,8 @@ print('%.1f (%.1f..%.1f) march %.4f trk %.4f' % (d['value'], d['value_min'], d['
 for rep in 1 2 3; do
   for v in base w6b3 w6b2; do
     if [ $v = base ]; then cp /tmp/base.so $L; a=-1; else cp octree-slam_amd/_variants/libsvoslam_hip_$v.so $L; a=90; fi
-    echo -n "$v rep $rep  20: "; SVOSLAM_CONFIG=march_ahead=$a python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
-    echo -n "$v rep $rep 100: "; SVOSLAM_CONFIG=march_ahead=$a python bench.py --steps 100 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
+    echo -n "$v rep $rep  20: "; SVOSLAM_CONFIG=march_ahead=$a python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
+    echo -n "$v rep $rep 100: "; SVOSLAM_CONFIG=march_ahead=$a python bench.py --full --steps 100 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
   done
 done
 cp /tmp/base.so $L

@@ -9,9 +9,9 @@ import sys, json
 d = json.loads(sys.stdin.read())
 print('%.1f frames/s (%.1f..%.1f) march %.4f ms tracker %.4f ms' % (d['value'], d['value_min'], d['value_max'], d['roofline_stages'][0]['kernel_ms'], d['roofline_stages'][1]['kernel_ms']), d.get('stages_sequential', {}).get('march_ms'))"; }
 run() {
-  echo -n "  cfg3 100: "; SVOSLAM_CONFIG=march_ahead=$1 python bench.py --steps 100 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
-  echo -n "  cfg3 20:  "; SVOSLAM_CONFIG=march_ahead=$1 python bench.py --steps 20 --warmup 5 --repeats 5 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
-  echo -n "  cfg4 40:  "; SVOSLAM_CONFIG=march_ahead=$1 python bench.py --workload cfg4 --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
+  echo -n "  cfg3 100: "; SVOSLAM_CONFIG=march_ahead=$1 python bench.py --full --steps 100 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
+  echo -n "  cfg3 20:  "; SVOSLAM_CONFIG=march_ahead=$1 python bench.py --full --steps 20 --warmup 5 --repeats 5 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
+  echo -n "  cfg4 40:  "; SVOSLAM_CONFIG=march_ahead=$1 python bench.py --full --workload cfg4 --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
 }
 {
 echo "== base, march_ahead=-1"; run -1

@@ -11,10 +11,10 @@ print('%.1f (%.1f..%.1f) frames/s; frames with shared records %s; delta bytes/fr
 {
 for wl in cfg3 cfg4; do
   st=40; [ $wl = cfg3 ] && st=100
-  echo -n "$wl single GPU: "; python bench.py --workload $wl --steps $st --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
+  echo -n "$wl single GPU: "; python bench.py --full --workload $wl --steps $st --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
   for ex in deltas keyrange; do
     for rk in 3/8 1/4 1/2; do [ -n "$KR_ONLY" ] && [ "$ex$rk" != "keyrange3/8" ] && [ "$ex$rk" != "keyrange1/2" ] && continue
-      echo -n "$wl $ex rank $rk: "; timeout 900 python bench.py --workload $wl --steps $st --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean --exchange $ex --emulate-rank $rk 2>$O/err_${wl}_${ex}_${rk/\//of}.txt | tee $O/bench_${wl}_${ex}_${rk/\//of}.json | line
+      echo -n "$wl $ex rank $rk: "; timeout 900 python bench.py --full --workload $wl --steps $st --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean --exchange $ex --emulate-rank $rk 2>$O/err_${wl}_${ex}_${rk/\//of}.txt | tee $O/bench_${wl}_${ex}_${rk/\//of}.json | line
     done
   done
 done

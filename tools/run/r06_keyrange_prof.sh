@@ -6,7 +6,7 @@ cd /tmp; export TMPDIR=/tmp
 for wl in cfg4 cfg3; do
   st=20; [ $wl = cfg3 ] && st=60
   D=/tmp/kr_$wl; rm -rf $D
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $D -o p -- python $R/bench.py --workload $wl --steps $st --warmup 5 --repeats 1 --no-cpu-baseline --no-other-configs --lean --exchange keyrange --emulate-rank 3/8 > $O/prof_$wl.log 2>&1
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $D -o p -- python $R/bench.py --full --workload $wl --steps $st --warmup 5 --repeats 1 --no-cpu-baseline --no-other-configs --lean --exchange keyrange --emulate-rank 3/8 > $O/prof_$wl.log 2>&1
   f=$(find $D -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $O/kernel_stats_keyrange_3of8_$wl.csv
   t=$(find $D -name "*kernel_trace.csv" | head -1)

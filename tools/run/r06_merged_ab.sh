@@ -15,9 +15,9 @@ for rep in 1 2 3; do
   for v in plain sep merged merged60 merged130; do
     a=90
     case $v in plain) cp /tmp/base.so $L; a=-1;; sep) cp octree-slam_amd/_variants/libsvoslam_hip_w6b3.so $L;; merged) cp /tmp/base.so $L;; merged60) cp /tmp/base.so $L; a=60;; merged130) cp /tmp/base.so $L; a=130;; esac
-    echo -n "$v rep $rep  20: "; SVOSLAM_CONFIG=march_ahead=$a python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
-    echo -n "$v rep $rep 100: "; SVOSLAM_CONFIG=march_ahead=$a python bench.py --steps 100 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
-    [ $rep = 1 ] && { echo -n "$v rep $rep cfg4: "; SVOSLAM_CONFIG=march_ahead=$a python bench.py --workload cfg4 --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line; }
+    echo -n "$v rep $rep  20: "; SVOSLAM_CONFIG=march_ahead=$a python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
+    echo -n "$v rep $rep 100: "; SVOSLAM_CONFIG=march_ahead=$a python bench.py --full --steps 100 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
+    [ $rep = 1 ] && { echo -n "$v rep $rep cfg4: "; SVOSLAM_CONFIG=march_ahead=$a python bench.py --full --workload cfg4 --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line; }
   done
 done
 cp /tmp/base.so $L

@@ -14,8 +14,8 @@ timeout 1700 python -m pytest tests/test_gpu_rgbd.py tests/test_gpu_configs.py t
 for rep in 1 2 3; do
   for v in base jonly new; do
     case $v in new) cp /tmp/new.so $L;; *) cp octree-slam_amd/_variants/libsvoslam_hip_$v.so $L;; esac
-    echo -n "$v rep $rep cfg3 100: "; python bench.py --steps 100 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs 2>/dev/null | line
-    echo -n "$v rep $rep cfg4  40: "; python bench.py --workload cfg4 --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs 2>/dev/null | line
+    echo -n "$v rep $rep cfg3 100: "; python bench.py --full --steps 100 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs 2>/dev/null | line
+    echo -n "$v rep $rep cfg4  40: "; python bench.py --full --workload cfg4 --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs 2>/dev/null | line
   done
 done
 cp /tmp/new.so $L

@@ -13,9 +13,9 @@ print('%.1f (%.1f..%.1f) march %.4f trk %.4f | alone: sort %.3f plan %.3f commit
 for rep in $(seq ${REPS:-3}); do
   for v in base ${VARIANTS}; do
     if [ $v = base ]; then cp /tmp/base.so $L; else cp octree-slam_amd/_variants/libsvoslam_hip_$v.so $L; fi
-    echo -n "$v rep $rep  20: "; python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
-    echo -n "$v rep $rep 100: "; python bench.py --steps 100 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
-    [ -n "$CFG4" ] && { echo -n "$v rep $rep cfg4: "; python bench.py --workload cfg4 --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line; }
+    echo -n "$v rep $rep  20: "; python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
+    echo -n "$v rep $rep 100: "; python bench.py --full --steps 100 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line
+    [ -n "$CFG4" ] && { echo -n "$v rep $rep cfg4: "; python bench.py --full --workload cfg4 --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --no-other-configs --lean 2>/dev/null | line; }
   done
 done
 cp /tmp/base.so $L
