@@ -65,10 +65,10 @@ typedef struct svoslam_config {
   int32_t runner_deferred;  /* frame scheduler: deferred commits -1 automatic (on up to 640x480-class images), 0, 1 */
   int32_t runner_lead;      /* commits the host may run ahead of the device: -1 automatic */
   int32_t runner_prio;      /* stream priorities (map stream highest): -1 automatic, 0, 1 */
-  int32_t runner_replicas;  /* 1, or 2 map replicas marched alternately (measured slower on one GPU: DESIGN.md) */
+  int32_t runner_replicas;  /* retired; must be 1 (two map replicas marched alternately were measured slower: DESIGN.md) */
   int32_t runner_timeline;  /* 1: HIP-event marks at the stage boundaries (svoslam_runner_timeline); costs ~6 % */
   int32_t sort_pairs;       /* 1: force the (key, index) pair sort instead of the packed one-word sort */
-  int32_t graphs;           /* 1: launch sequences recorded and replayed as HIP graphs (0: direct launches, the default) */
+  int32_t graphs;           /* retired; must be 0 (launch sequences replayed as graphs were measured slower: DESIGN.md) */
   int32_t march_ahead;      /* brick march: n >= 0 (default 60): past its first n steps a ray is marched in BURSTS of three samples -- the
                                current one and two reached by advancing with the previous step's level, their entries requested
                                together -- and follows the burst as long as each step ends on that level (results identical; overlaps
@@ -103,8 +103,7 @@ typedef struct {
 int svoslam_pool_init(svoslam_pool *pool, int32_t capacity_nodes, void *stream);
 int svoslam_pool_reserve(svoslam_pool *pool, int32_t capacity_nodes, void *stream);
 int svoslam_pool_free(svoslam_pool *pool);
-/* back to the 8 zeroed root children of initOctree; the allocation (and with it every launch graph the
- * library has recorded against this pool) is kept.  Blocking: waits for the whole device. */
+/* back to the 8 zeroed root children of initOctree; the allocation is kept.  Blocking: waits for the whole device. */
 int svoslam_pool_reset(svoslam_pool *pool, void *stream);
 /* makes pool->size exact again after asynchronous fusion calls (one stream sync + 4-byte readback) */
 int svoslam_pool_sync(svoslam_pool *pool, void *stream);
@@ -190,7 +189,7 @@ int svoslam_svo_from_point_cloud_async(svoslam_workspace *ws, const float *d_poi
  * previous state (svoFromPointCloud then coneTraceSVO per frame, src/main.cpp:44,56):
  *   sort   keys + sort of the points; touches only the workspace
  *   plan   reads the pool's tree (must follow the previous commit; may run while the pool is ray-marched)
- *   commit writes the pool (splits, leaf blend, mip levels)
+ *   commit writes the pool (splits, leaf blend, mip levels) and consumes the plan
  * sort -> plan -> commit on one workspace == svoslam_svo_from_point_cloud_async.  Fusions in flight at
  * the same time need a workspace each.  If plan has to grow the pool it first waits for the whole device. */
 int svoslam_svo_fuse_sort(svoslam_workspace *ws, const float *d_points, int32_t n, int32_t max_depth,
@@ -239,12 +238,6 @@ int svoslam_svo_fuse_split_early(svoslam_workspace *ws, int32_t n, int32_t max_d
  * sequence, ordered after everything earlier on the pool.  Same pool contents as plan + commit per frame. */
 int svoslam_pool_structure_begin(svoslam_pool *pool, void *stream);
 int svoslam_svo_fuse_plan_structure(svoslam_workspace *ws, int32_t n, int32_t max_depth, svoslam_pool *pool, void *stream);
-/* The planned commit applied to one of several BYTE-IDENTICAL replicas of a map (a plan made against any replica in
- * the state before this commit fits all of them: same tree, same tile numbering).  Each application uses its own
- * slot (0 or 1; applications with different slots may run concurrently), all but the last pass keep_plan != 0.
- * Replicas must have been given the same capacity.  svoslam_svo_fuse_commit == (slot 0, keep_plan 0). */
-int svoslam_svo_fuse_commit_to(svoslam_workspace *ws, const uint8_t *d_colors, int32_t n, int32_t max_depth,
-                               svoslam_pool *pool, int32_t slot, int32_t keep_plan, void *stream);
 /* The commit in two halves, for callers that ray-march the map while the next frame is being fused (the frame
  * scheduler): svoslam_svo_fuse_commit_deferred does all the work of the commit -- splitNodes, fillNodes, mipmapNodes,
  * svo.cu:239-465 -- without a store a concurrent cone trace of the pool in its present state can observe (new tiles
@@ -547,7 +540,7 @@ typedef struct svoslam_camera svoslam_camera;
  * the image rows this process owns for ICP accumulation (0, height = all). */
 int svoslam_camera_create(svoslam_camera **cam, int32_t width, int32_t height, float fx, float fy);
 int svoslam_camera_destroy(svoslam_camera *cam);
-/* back to a new RGBDCamera (identity pose, no frame seen) keeping buffers and recorded launch graphs.  Blocking. */
+/* back to a new RGBDCamera (identity pose, no frame seen) keeping its buffers.  Blocking. */
 int svoslam_camera_reset(svoslam_camera *cam);
 int svoslam_camera_set_band(svoslam_camera *cam, int32_t first_row, int32_t rows);
 /* RGBDCamera::update, rgbd_camera.cpp:53-191.  Non-blocking.  Returns 1 in
@@ -682,7 +675,7 @@ int svoslam_runner_run(svoslam_runner *runner, const uint16_t *const *d_depths, 
  * per frame); *models_used (optional) = frames whose model was accepted.  Same call rules as svoslam_runner_run (one caller stream
  * per runner, timestamps newer than the camera's latest).  Leaves frame-to-model tracking switched on in the camera and the last
  * accepted model set, so that a second call continues the sequence as one longer call would; a later svoslam_runner_run on the
- * same runner -- the loop without a model refresh -- clears both when it starts and tracks frame to frame.  One replica only. */
+ * same runner -- the loop without a model refresh -- clears both when it starts and tracks frame to frame. */
 int svoslam_runner_run_model(svoslam_runner *runner, const uint16_t *const *d_depths, const uint8_t *const *d_rgbs,
                              const long long *timestamps, const float *views, int32_t n, uint8_t *d_image, int32_t row_first,
                              int32_t rows, unsigned long long *d_steps, float min_coverage, int32_t *models_used, void *caller_stream);
@@ -695,8 +688,8 @@ int svoslam_runner_bbox(svoslam_runner *runner, float h_bbox7[7]);
  * all-gathered; delta_events (optional; n hipEvent_t, NULL entries allowed): what the pose stream waits for before it reads
  * d_deltas[i] -- so the runner's camera never sees a depth image; EVERY frame is back-projected, planned and committed
  * (the replicas stay byte-identical), and only the frames with march[i] != 0 (march = NULL: all) are ray-marched, frame i
- * into d_images[i].  Entry 0 of d_deltas is ignored for a camera's first frame.  Needs the default one-replica,
- * direct-commit schedule. */
+ * into d_images[i].  Entry 0 of d_deltas is ignored for a camera's first frame.  Needs the direct-commit schedule (not an
+ * explicit runner_deferred = 1). */
 int svoslam_runner_run_sharded(svoslam_runner *runner, const uint16_t *const *d_depths, const uint8_t *const *d_rgbs,
                                const long long *timestamps, const float *views, int32_t n, const float *const *d_deltas,
                                void *const *delta_events, const uint8_t *march, uint8_t *const *d_images, int32_t row_first,

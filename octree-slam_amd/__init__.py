@@ -100,7 +100,6 @@ SIGNATURES = {
     "svoslam_svo_fuse_merge_sorted": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), _i32, _vp, _vp, _vp]),
     "svoslam_svo_fuse_export_sorted": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),
     "svoslam_pool_structure_begin": (C.c_int, [C.POINTER(_PoolStruct), _vp]),
-    "svoslam_svo_fuse_commit_to": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(_PoolStruct), _i32, _i32, _vp]),
     "svoslam_svo_fuse_commit_deferred": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(_PoolStruct), _vp]),
     "svoslam_svo_fuse_apply": (C.c_int, [_vp, C.POINTER(_PoolStruct), _vp]),
     "svoslam_svo_fuse_keyrange_commit": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, C.POINTER(_PoolStruct), _i32, _i32, _vp, C.c_int64, _vp]),
@@ -296,7 +295,7 @@ def get_config():
 
 
 def configure(**settings):
-    """svoslam_config_set: e.g. configure(track_mode=1, graphs=1); takes effect for cameras / runners created afterwards and
+    """svoslam_config_set: e.g. configure(track_mode=1, runner_deferred=0); takes effect for cameras / runners created afterwards and
     for the next render / fusion call.  Returns the settings as they were."""
     c = ConfigStruct()
     check(lib().svoslam_config_get(C.byref(c)))
@@ -522,13 +521,6 @@ def svo_fuse_commit(ws, colors, max_depth, pool):
     """phase 3: splits, leaf blend, mip levels (writes the pool)."""
     n = int(colors.shape[0]) if colors is not None else 0
     check(lib().svoslam_svo_fuse_commit(ws._h, _ptr(colors), n, max_depth, C.byref(pool._p), _stream()))
-
-
-def svo_fuse_commit_to(ws, colors, max_depth, pool, slot, keep_plan):
-    """phase 3 applied to one of several identical replicas of the map (see svoslam.h)"""
-    n = int(colors.shape[0]) if colors is not None else 0
-    check(lib().svoslam_svo_fuse_commit_to(ws._h, _ptr(colors), n, max_depth, C.byref(pool._p), int(slot), 1 if keep_plan else 0,
-                                           _stream()))
 
 
 def svo_fuse_commit_deferred(ws, colors, max_depth, pool):
@@ -1177,7 +1169,7 @@ class Camera:
         check(lib().svoslam_camera_set_frame_to_model(self._h, 1 if enable else 0))
 
     def reset(self):
-        """identity pose, no frame seen; buffers and recorded graphs kept"""
+        """identity pose, no frame seen; buffers kept"""
         check(lib().svoslam_camera_reset(self._h))
 
     def prepare(self, depth, rgb, timestamp):

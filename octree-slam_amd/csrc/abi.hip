@@ -228,11 +228,6 @@ int svoslam_svo_fuse_commit(svoslam_workspace *ws, const uint8_t *d_colors, int3
   NEED_DEVICE();
   return svo_fuse_commit(ws, d_colors, n, max_depth, pool, S(stream));
 }
-int svoslam_svo_fuse_commit_to(svoslam_workspace *ws, const uint8_t *d_colors, int32_t n, int32_t max_depth, svoslam_pool *pool,
-                               int32_t slot, int32_t keep_plan, void *stream) {
-  NEED_DEVICE();
-  return svo_fuse_commit_to(ws, d_colors, n, max_depth, pool, slot, keep_plan != 0, S(stream));
-}
 int svoslam_svo_fuse_commit_deferred(svoslam_workspace *ws, const uint8_t *d_colors, int32_t n, int32_t max_depth, svoslam_pool *pool,
                                      void *stream) {
   NEED_DEVICE();

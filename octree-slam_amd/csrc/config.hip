@@ -23,7 +23,7 @@ const Field kFields[] = {
 };
 
 bool config_valid(const svoslam_config &c) {
-  if (c.runner_replicas != 1 && c.runner_replicas != 2) return false;
+  if (c.runner_replicas != 1 || c.graphs != 0) return false;  // retired options: only their defaults remain
   if (c.track_mode < 0 || c.track_mode > 2 || c.track_workers < 0) return false;
   return true;
 }

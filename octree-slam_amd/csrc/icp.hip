@@ -26,7 +26,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "graph_cache.hpp"
 #include "config.hpp"
 #include "icp.hpp"
 #include "icp_device.hpp"
@@ -536,7 +535,6 @@ struct svoslam_camera {
   double *d_partial = nullptr;  // per-workgroup rows of the accumulate kernel
   bool frame_has_icp = false;
   int ring_slot = 0;       // fusion_ring slot of the frame being / last tracked
-  svoslam::GraphCache g_prep, g_track;  // recorded launch sequences (graph_cache.hpp)
   // photometric RGB-D term (off by default = the reference, which ships it commented out): intensity and Sobel
   // gradient pyramids per map set, rows of the photometric accumulate kernel
   bool rgbd = false;
@@ -593,8 +591,8 @@ int camera_create(svoslam_camera **out, int w, int h, float fx, float fy) {
   return SVOSLAM_OK;
 }
 
-// back to the state of a new RGBDCamera (pose identity, no frame seen); device buffers and the recorded
-// launch graphs are kept.  Blocking (waits for the device).
+// back to the state of a new RGBDCamera (pose identity, no frame seen); device buffers are kept.  Blocking (waits for
+// the device).
 int camera_reset(svoslam_camera *c) {
   if (!c) return SVOSLAM_ERR_INVALID_ARG;
   SVO_HIP(hipDeviceSynchronize());
@@ -688,11 +686,9 @@ int camera_prepare(svoslam_camera *c, const uint16_t *d_depth, const uint8_t *d_
   c->latest_stamp = timestamp;
   if (processed) *processed = 1;
   const int set = (int)(c->prepared % 3u);
-  GraphKey key;
-  key.add(d_depth).add((unsigned long long)set).add(c->rgbd ? d_rgb : nullptr);
   {
     StageScope timed(kStageMaps, s);
-    SVO_TRY(c->g_prep.run(key, s, [&]() -> int { return enqueue_preprocess(c, d_depth, d_rgb, set, s); }));
+    SVO_TRY(enqueue_preprocess(c, d_depth, d_rgb, set, s));
   }
   c->prepared++;
   return SVOSLAM_OK;
@@ -796,7 +792,7 @@ static int track_one_launch(svoslam_camera *c, hipStream_t s) {
   if (c->capacity < 2) return 1;  // no room for a solver and a worker workgroup on this stream's CUs: the launch chain
   SVO_TRY(track_persistent_plan(A, c->capacity));
   if (A.slots[0] > kTrkSlots && !track_one_launch_forced() && track_stream_enabled()) {
-    // the streaming one-launch form (track_persistent.hip): work maps allocated on first use (before any capture)
+    // the streaming one-launch form (track_persistent.hip): work maps allocated on first use
     if (!c->work_v) {
       const size_t n = (size_t)c->width * (size_t)c->height;
       SVO_HIP(hipMalloc((void **)&c->work_v, n * 12));
@@ -836,55 +832,45 @@ int camera_track(svoslam_camera *c, hipStream_t s) {
     }
     if (rc >= 2) top_level = rc - 2;  // hybrid: the coarser levels are already enqueued
   }
-  // Work maps: allocated on the first chain-tracked frame (cameras served by the one-launch tracker never pay for them),
-  // before any capture
+  // Work maps: allocated on the first chain-tracked frame (cameras served by the one-launch tracker never pay for them)
   const bool work_maps = true;
   if (has_icp && !c->work_v) {
     const size_t n = (size_t)c->width * (size_t)c->height;
     SVO_HIP(hipMalloc((void **)&c->work_v, n * 12));
     SVO_HIP(hipMalloc((void **)&c->work_n, n * 12));
   }
-  GraphKey key;
-  key.add((unsigned long long)(c->tracked % 3u)).add((unsigned long long)has_icp)
-     .add((unsigned long long)c->band_first).add((unsigned long long)c->band_rows).add((unsigned long long)c->rgbd)
-     .add((unsigned long long)work_maps).add((unsigned long long)top_level).add((unsigned long long)(c->to_model && c->have_model))
-     .add((unsigned long long)c->corrected);
-  auto enqueue = [&]() -> int {
-    if (has_icp) {
-      for (int level = top_level; level >= 0; level--) {  // coarse to fine, :103
-        LevelArgs a = level_args(c, level);
-        int end;
-        const int blocks = accumulate_range(a.w, a.h, a.first, a.num, end);
-        const int cur = (int)(c->tracked % 3u), last = (int)((c->tracked + 2u) % 3u);
-        int blocks2 = (int)cdiv(a.w * a.h, kIcpThreads);
-        if (blocks2 > kMaxIcpBlocks) blocks2 = kMaxIcpBlocks;
-        for (int it = 0; it < kPyramidIters[level]; it++) {
-          const int flags = iter_flags(level, it);
-          if (work_maps) {
-            // iteration it > 0 reads what iteration it - 1 stored (level start and chain[0 .. it - 1) applied) and applies
-            // chain[it - 1]; the last iteration of a level stores nothing
-            const bool store = it + 1 < kPyramidIters[level];
-            icp_accumulate_work_kernel<<<blocks, kIcpThreads, 0, s>>>(a.lv, a.ln, it ? c->work_v : a.cv, it ? c->work_n : a.cn, a.first, end,
-                                                                      c->d_state, flags, it, it, store ? c->work_v : nullptr,
-                                                                      store ? c->work_n : nullptr, c->d_partial);
-          } else {
-            icp_accumulate_kernel<<<blocks, kIcpThreads, 0, s>>>(a.lv, a.ln, a.cv, a.cn, a.first, end, c->d_state, flags, it,
-                                                                 c->d_partial);
-          }
-          if (c->rgbd)  // rgbd_camera.cpp:126-128 (there commented out): the photometric system of the same estimate
-            rgbd_accumulate_kernel<<<blocks2, kIcpThreads, 0, s>>>(c->inten[last][level], c->grad[last][level], a.lv, c->inten[cur][level],
-                                                                   a.cv, 0, a.w * a.h, c->fx, c->fy, (float)(c->width / a.w),
-                                                                   (float)(c->height / a.h), c->d_state, flags, it, c->d_partial2);
-          cam_reduce_solve_kernel<<<1, kReduceThreads, 0, s>>>(c->d_state, c->d_partial, blocks, it, flags, c->rgbd ? c->d_partial2 : nullptr, blocks2);
+  if (has_icp) {
+    for (int level = top_level; level >= 0; level--) {  // coarse to fine, :103
+      LevelArgs a = level_args(c, level);
+      int end;
+      const int blocks = accumulate_range(a.w, a.h, a.first, a.num, end);
+      const int cur = (int)(c->tracked % 3u), last = (int)((c->tracked + 2u) % 3u);
+      int blocks2 = (int)cdiv(a.w * a.h, kIcpThreads);
+      if (blocks2 > kMaxIcpBlocks) blocks2 = kMaxIcpBlocks;
+      for (int it = 0; it < kPyramidIters[level]; it++) {
+        const int flags = iter_flags(level, it);
+        if (work_maps) {
+          // iteration it > 0 reads what iteration it - 1 stored (level start and chain[0 .. it - 1) applied) and applies
+          // chain[it - 1]; the last iteration of a level stores nothing
+          const bool store = it + 1 < kPyramidIters[level];
+          icp_accumulate_work_kernel<<<blocks, kIcpThreads, 0, s>>>(a.lv, a.ln, it ? c->work_v : a.cv, it ? c->work_n : a.cn, a.first, end,
+                                                                    c->d_state, flags, it, it, store ? c->work_v : nullptr,
+                                                                    store ? c->work_n : nullptr, c->d_partial);
+        } else {
+          icp_accumulate_kernel<<<blocks, kIcpThreads, 0, s>>>(a.lv, a.ln, a.cv, a.cn, a.first, end, c->d_state, flags, it,
+                                                               c->d_partial);
         }
+        if (c->rgbd)  // rgbd_camera.cpp:126-128 (there commented out): the photometric system of the same estimate
+          rgbd_accumulate_kernel<<<blocks2, kIcpThreads, 0, s>>>(c->inten[last][level], c->grad[last][level], a.lv, c->inten[cur][level],
+                                                                 a.cv, 0, a.w * a.h, c->fx, c->fy, (float)(c->width / a.w),
+                                                                 (float)(c->height / a.h), c->d_state, flags, it, c->d_partial2);
+        cam_reduce_solve_kernel<<<1, kReduceThreads, 0, s>>>(c->d_state, c->d_partial, blocks, it, flags, c->rgbd ? c->d_partial2 : nullptr, blocks2);
       }
-    } else {  // first frame: no ICP, only the fusion transform (the last solve does it otherwise)
-      cam_frame_end_kernel<<<1, 64, 0, s>>>(c->d_state, 0);
     }
-    SVO_LAUNCH_CHECK();
-    return SVOSLAM_OK;
-  };
-  SVO_TRY(c->g_track.run(key, s, enqueue));
+  } else {  // first frame: no ICP, only the fusion transform (the last solve does it otherwise)
+    cam_frame_end_kernel<<<1, 64, 0, s>>>(c->d_state, 0);
+  }
+  SVO_LAUNCH_CHECK();
   c->ring_slot = ring_slot;
   c->tracked++;
   c->frame_has_icp = false;
@@ -915,9 +901,7 @@ int camera_pair_delta(svoslam_camera *c, const uint16_t *d_depth_prev, const uin
   for (int set = 0; set < 2; set++) {
     const uint16_t *d = set ? d_depth_cur : d_depth_prev;
     const uint8_t *rgb = set ? d_rgb_cur : d_rgb_prev;
-    GraphKey key;
-    key.add(d).add((unsigned long long)set).add(c->rgbd ? rgb : nullptr);
-    SVO_TRY(c->g_prep.run(key, s, [&]() -> int { return enqueue_preprocess(c, d, rgb, set, s); }));
+    SVO_TRY(enqueue_preprocess(c, d, rgb, set, s));
   }
   c->prepared = 2; c->tracked = 1;  // level_args(): current maps = set 1, last maps = set 0
   const int rc = camera_track(c, s);

@@ -11,8 +11,6 @@ int radix_sort_num_tiles(int n);
 // iota_vals = false: the values to carry are in ws->vals_a.
 int radix_sort_pairs(svoslam_workspace *ws, int n, int num_bits, hipStream_t stream,
                      unsigned long long **sorted_keys, unsigned **sorted_vals, bool iota_vals = true);
-// Where that sort leaves its result (depends only on the pass count).
-int radix_sort_output(svoslam_workspace *ws, int n, int num_bits, unsigned long long **sorted_keys, unsigned **sorted_vals);
 // Packed form (see radix_sort.hip): n words (key << idx_bits | index) in ws->keys_a, first-pass histograms in
 // ws->tile_hist ([tile][1 << radix_packed_first_bits(key_bits)] for tiles of radix_packed_tile() elements; reserve
 // radix_packed_hist_words(n) words).  Output: unpacked keys in keys_a / keys_b, indices in vals_a.
@@ -33,7 +31,6 @@ int radix_sort_packed(svoslam_workspace *ws, int n, int key_bits, int idx_bits, 
 int radix_sort_packed_ex(svoslam_workspace *ws, int n, int key_bits, int idx_bits, int max_bits, bool have_first_hist, bool want_vals,
                          hipStream_t stream, unsigned long long **sorted_keys, unsigned **sorted_vals);
 int radix_packed_digit_bits_for(long long n);  // the digit width radix_sort_packed_ex callers use for n elements
-int radix_sort_packed_output(svoslam_workspace *ws, int key_bits, unsigned long long **sorted_keys, unsigned **sorted_vals);
 // In-place exclusive scan of each of 256 rows of num_tiles counters; row totals to totals[256].
 void row_scan_rows(unsigned *rows, int num_tiles, unsigned *totals, hipStream_t stream);
 // Same for a single row.

@@ -1,32 +1,21 @@
 // runner.hip -- native frame scheduler of the SLAM loop (main.cpp:31-84 per frame: track -> back-project ->
-// fuse -> raycast), software-pipelined over HIP streams:
+// fuse -> raycast), software-pipelined over five HIP streams:
 //
 //   P   bilateral filter + vertex/normal pyramids of frame k+2 (three rotating map sets in the camera)
 //   T   the ICP iterations of frame k+1 (one launch); touches only the camera state
-//   S   back-projection, keys + sort and split planning of frame k+1 (reads a pool's tree)
-//   M0  commits to replica 0 of the map, raycasts of the even frames
-//   M1  commits to replica 1 of the map, raycasts of the odd frames
+//   S   back-projection, keys + sort and split planning (+ early split) of frame k+1 (reads the pool's tree)
+//   C   deferred commit of frame k+1: splits beyond the pool's size, colour words to the shadow array (deferred schedule only)
+//   M   apply of that commit (in place: the whole commit) + grid / brick refresh + ray march of frame k
 //
-// Two replicas of the map.  A frame's raycast (~0.3 ms: bound by the dependent-load latency of its longest rays, not by
-// CUs) and the next frame's commit cannot touch one pool at the same time, and with one pool their sum is the frame
-// period.  The scheduler therefore keeps a second, byte-identical replica of the caller's pool: every plan is applied
-// to both (svoslam_svo_fuse_commit_to -- the commit is a deterministic function of plan + pool, so the replicas stay
-// identical), and the frames are ray-marched on them alternately.  While frame k is marched on replica k & 1 the
-// commits of frames k+1 and k+2 go to the other one, so each replica carries two commits and one raycast per TWO
-// frames.  Cost: the commit kernels run twice and the map takes twice the HBM (a few GB of 288).
-// MEASURED (round 2, cfg3, profiles/r02_runner_timeline_*.txt): with ONE replica the M stream bounds the frame at
-// commit 0.133 ms + build/march 0.272 ms = 0.405 ms; with TWO the replica streams do overlap but every kernel gets
-// slower -- march 0.27 -> 0.41 ms, commit 0.13 -> 0.22-0.29 ms, maps 0.10 -> 0.37 ms -- because the march keeps
-// ~4800 wavefronts (66 % of the VGPR file) resident for its whole duration and the tracker's 151 workgroups want
-// the other half: 0.52-0.55 ms per frame against 0.41-0.43.  The schedule is therefore OPT-IN (svoslam_config.runner_replicas = 2;
-// it is also the single-GPU form of pipelining the stages over several GPUs, where each replica has a GPU to itself);
-// the default is one pool.
+// Only M changes what a march can see.  Deferred commits are the default on images up to 640x480-class, in-place commits
+// (the plan on P) above.  One pool: a second replica of the map marched on alternate frames was measured slower and removed
+// (profiles/HISTORY_r01_r03.md).
 //
-// Cross-stream order (events): S waits for the pose of its frame (from T) and, before planning, for commit k-1 on the
-// replica it reads; an M stream waits for the plan of the frame it commits; T waits, before it overwrites a slot of
-// the 4-deep pose ring, for the back-projection that read that slot; P waits for the pose of frame k-2 (whose "last"
-// map set it overwrites); S waits, before it reuses a workspace / point buffer / colour staging buffer (rings of three),
-// for both commits of the frame that used them.  Results are those of calling the stages one after the other.
+// Cross-stream order (events): S waits for the pose of its frame (from T) and, before planning, for commit k-1; M (and C)
+// wait for the plan of the frame they commit; T waits, before it overwrites a slot of the 4-deep pose ring, for the
+// back-projection that read that slot; P waits for the pose of frame k-2 (whose "last" map set it overwrites); S waits,
+// before it reuses a workspace / point buffer (rings of three), for the commit of the frame that used them.  Results are
+// those of calling the stages one after the other.
 //
 // Built on the public C ABI (include/svoslam.h) only: every stage is the call a reference-style host would make.
 #include <hip/hip_runtime.h>
@@ -43,7 +32,7 @@
 #include "../../include/svoslam.h"
 
 namespace {
-constexpr int kRing = 3;  // frames whose fusion may be in flight: workspaces, point clouds, colour staging
+constexpr int kRing = 3;  // frames whose fusion may be in flight: workspaces, point clouds
 }
 
 // stream sets of destroyed runners, by kind (see svoslam_runner_create)
@@ -52,20 +41,14 @@ static std::map<int, std::vector<std::array<hipStream_t, 5>>> g_free_streams;
 
 struct svoslam_runner {
   svoslam_camera *cam = nullptr;
-  svoslam_pool *pool = nullptr;     // replica 0: the caller's pool
-  svoslam_pool replica1;            // replica 1 (owned); d_data == nullptr while unused
-  int replicas = 1;
+  svoslam_pool *pool = nullptr;     // the caller's pool
   int w = 0, h = 0, depth = 0, mode = 0;
   float center[3] = {0, 0, 0}, edge = 0, fx = 0, fy = 0, fov = 45.0f;
   hipStream_t s_maps = nullptr, s_track = nullptr, s_prep = nullptr, s_map[2] = {nullptr, nullptr};
   svoslam_workspace *ws[kRing] = {nullptr, nullptr, nullptr};
   float *points[kRing] = {nullptr, nullptr, nullptr};  // back-projected clouds of the frames in flight
-  uint8_t *in_rgb[kRing] = {nullptr, nullptr, nullptr};
   float *bbox = nullptr;                   // 7 floats (main.cpp:44)
-  uint8_t *scratch_image[2] = {nullptr, nullptr};  // raycasts of all but the last frame of a call
-  // fixed input addresses per stream: the library replays its launch sequences as HIP graphs keyed on the
-  // pointers it is given (graph_cache.hpp), so every frame is copied into a staging buffer first
-  uint16_t *in_track = nullptr, *in_prep = nullptr;
+  uint8_t *scratch_image = nullptr;       // raycasts of all but the last frame of a call
   uint16_t *model_depth = nullptr;         // svoslam_runner_run_model: the map ray-cast from the pose just tracked
   unsigned *model_count = nullptr;         // ... and the number of its pixels that met the map
   std::vector<hipEvent_t> events;  // pool, grown on demand
@@ -75,7 +58,7 @@ struct svoslam_runner {
   int lead = -1;  // commits the host may run ahead of the device (see svoslam_runner_run); < 0: the schedule's default (1 deferred, 2 in place)
   bool fused_front = false;  // back-projection + bounding box + keys in one launch (keys that do not fit the packed word: the stand-alone calls)
   bool early_split = true;  // split_all_kernel right behind the plan, beside the previous frame's march
-  // one replica: the commit of frame k+1 is computed during the march of frame k (svoslam_svo_fuse_commit_deferred).  Default
+  // the commit of frame k+1 is computed during the march of frame k (svoslam_svo_fuse_commit_deferred).  Default
   // since round 3 for images up to 640x480-class: the march over occupancy bricks is bound by instruction issue and no
   // longer by the loads the commit competes for (cfg3, 300-frame map: 1862 -> 2055 frames/s; the driver's 20 frames 1565 ->
   // 1707; cfg4, where the launch-chain tracker bounds the frame, 815 -> 694: off there).  svoslam_config.runner_deferred = 0 / 1 overrides.
@@ -89,7 +72,7 @@ struct svoslam_runner {
 };
 
 namespace { constexpr int kTlStages = 10; }
-  // maps0 maps1 track0 track1 prep0 plan0 plan1 commit0 commit1(first replica) ray1
+  // maps0 maps1 track0 track1 prep0 plan0 plan1 commit0 commit1 ray1
 
 namespace {
 
@@ -102,8 +85,6 @@ int ensure_events(svoslam_runner *r, size_t n) {
   return SVOSLAM_OK;
 }
 
-svoslam_pool *replica(svoslam_runner *r, int k) { return k == 0 ? r->pool : &r->replica1; }
-
 }  // namespace
 
 extern "C" {
@@ -113,15 +94,13 @@ int svoslam_runner_create(svoslam_runner **out, svoslam_camera *cam, svoslam_poo
   if (!out || !cam || !pool || !center || width <= 0 || height <= 0) return SVOSLAM_ERR_INVALID_ARG;
   if (max_depth < 1 || max_depth > SVOSLAM_MAX_DEPTH) return SVOSLAM_ERR_DEPTH;
   svoslam_runner *r = new svoslam_runner();
-  memset(&r->replica1, 0, sizeof(r->replica1));
   r->cam = cam; r->pool = pool; r->w = width; r->h = height; r->depth = max_depth; r->mode = render_mode;
   for (int k = 0; k < 3; k++) r->center[k] = center[k];
   r->edge = edge_length; r->fx = fx; r->fy = fy;
   const svoslam_config cfg = svoslam::config();  // (settings are taken when the runner is created)
-  r->replicas = cfg.runner_replicas == 2 ? 2 : 1;
   r->timeline = cfg.runner_timeline != 0;
   r->deferred_explicit = cfg.runner_deferred >= 0;
-  r->deferred = cfg.runner_deferred >= 0 ? cfg.runner_deferred == 1 : ((long long)width * height <= 400000ll && r->replicas == 1);
+  r->deferred = cfg.runner_deferred >= 0 ? cfg.runner_deferred == 1 : (long long)width * height <= 400000ll;
   {
     int idx_bits = 1;
     while ((1ll << idx_bits) < (long long)width * height) idx_bits++;
@@ -171,13 +150,10 @@ int svoslam_runner_create(svoslam_runner **out, svoslam_camera *cam, svoslam_poo
   for (int k = 0; k < kRing; k++) {
     SVO_TRY(svoslam_workspace_create(&r->ws[k]));
     SVO_HIP(hipMalloc((void **)&r->points[k], n * 12));
-    SVO_HIP(hipMalloc((void **)&r->in_rgb[k], n * 3));
   }
-  for (int k = 0; k < 2; k++) SVO_HIP(hipMalloc((void **)&r->scratch_image[k], n * 4));
+  SVO_HIP(hipMalloc((void **)&r->scratch_image, n * 4));
   SVO_HIP(hipMalloc((void **)&r->bbox, 7 * 4));
   SVO_HIP(svoslam::memset_sync(r->bbox, 0, 7 * 4));
-  SVO_HIP(hipMalloc((void **)&r->in_track, n * 2));
-  SVO_HIP(hipMalloc((void **)&r->in_prep, n * 2));
   SVO_HIP(hipEventCreateWithFlags(&r->ev_begin, hipEventDisableTiming));
   for (int k = 0; k < 5; k++) SVO_HIP(hipEventCreateWithFlags(&r->ev_end[k], hipEventDisableTiming));
   return SVOSLAM_OK;
@@ -193,10 +169,9 @@ int svoslam_runner_destroy(svoslam_runner *r) {
   for (int k = 0; k < kRing; k++) {
     if (r->ws[k]) svoslam_workspace_destroy(r->ws[k]);
     (void)hipFree(r->points[k]);
-    (void)hipFree(r->in_rgb[k]);
   }
-  for (int k = 0; k < 2; k++) (void)hipFree(r->scratch_image[k]);
-  (void)hipFree(r->bbox); (void)hipFree(r->in_track); (void)hipFree(r->in_prep);
+  (void)hipFree(r->scratch_image);
+  (void)hipFree(r->bbox);
   if (r->model_depth) (void)hipFree(r->model_depth);
   if (r->model_count) (void)hipFree(r->model_count);
   {
@@ -214,7 +189,6 @@ int svoslam_runner_destroy(svoslam_runner *r) {
       for (hipStream_t s : set) if (s) (void)hipStreamDestroy(s);
     }
   }
-  if (r->replica1.d_data) (void)svoslam_pool_free(&r->replica1);
   delete r;
   return SVOSLAM_OK;
 }
@@ -226,8 +200,7 @@ int svoslam_runner_destroy(svoslam_runner *r) {
 // earlier frames of the call are marched into internal buffers) -- the pool and the pose.
 // d_steps (optional): 2 x u64 step / level counters accumulated over all raycasts.
 // All arguments are validated BEFORE anything is enqueued; if a stage fails later, the streams are still joined to
-// caller_stream before the error is returned.  Calls on one runner must use one caller_stream (checked).  With two
-// replicas the call first brings replica 1 up to date with the caller's pool (blocking device copy).
+// caller_stream before the error is returned.  Calls on one runner must use one caller_stream (checked).
 //
 // Sharded form (svoslam_runner_run_sharded): d_deltas != nullptr.  The poses come from
 // svoslam_camera_apply_delta(d_deltas[i]) instead of the tracker -- the frames were tracked elsewhere (other ranks, other
@@ -251,7 +224,7 @@ static int runner_run_impl(svoslam_runner *r, const uint16_t *const *d_depths, c
   if (!r || n < 0 || (n > 0 && (!d_depths || !d_rgbs || !timestamps || !views || (!d_image && !d_images)))) return SVOSLAM_ERR_INVALID_ARG;
   if (n == 0) return SVOSLAM_OK;
   if (row_first < 0 || rows < 0 || row_first + rows > r->h) return SVOSLAM_ERR_INVALID_ARG;
-  if (sharded && (r->replicas != 1 || (r->deferred && r->deferred_explicit))) return SVOSLAM_ERR_INVALID_ARG;
+  if (sharded && r->deferred && r->deferred_explicit) return SVOSLAM_ERR_INVALID_ARG;
   const bool deferred = r->deferred && !sharded;  // (frame-sharded sessions keep the in-place commit)
   if (d_images)
     for (int i = 0; i < n; i++)
@@ -273,16 +246,9 @@ static int runner_run_impl(svoslam_runner *r, const uint16_t *const *d_depths, c
     SVO_TRY(svoslam_camera_set_frame_to_model(r->cam, 0));
     r->model_pending = false;
   }
-  const size_t px = (size_t)r->w * r->h;
-  const int npts = (int)px;
-  const int R = r->replicas;
-  if (R == 2) {
-    // replica 1 := the caller's pool as it is now (the caller may have fused, loaded or reset it since the last call)
-    SVO_HIP(hipStreamSynchronize(cur));
-    const int rc = svoslam_pool_copy(&r->replica1, r->pool, cur);
-    if (rc != SVOSLAM_OK) return rc;
-  }
-  // events of this call: maps, pose, back-projection, plan of every frame; commit of every frame on every replica
+  const int npts = r->w * r->h;
+  // events of this call: maps, pose, back-projection, plan, commit, march, sort of every frame.  ev_commit[0]: the commit
+  // as the map stream applies it; ev_commit[1] (deferred schedule): the commit computed on stream C
   SVO_TRY(ensure_events(r, 8 * (size_t)n));
   hipEvent_t *ev_maps = r->events.data(), *ev_pose = ev_maps + n, *ev_bp = ev_pose + n, *ev_plan = ev_bp + n;
   hipEvent_t *ev_commit[2] = {ev_plan + n, ev_plan + 2 * (size_t)n};
@@ -290,8 +256,7 @@ static int runner_run_impl(svoslam_runner *r, const uint16_t *const *d_depths, c
   hipEvent_t *ev_sorted = ev_ray + n;
   // Large images with in-place commits (1920x1080): back-projection + sort alone fill the S stream (0.83 of the 1.05 ms period in the
   // scheduler's timeline, the plan the other 0.22), so the plan runs on the maps stream, which has 0.8 ms to spare: 932 -> 963 frames/s
-  const bool plan_on_maps = !sharded && !deferred && R == 1 && (long long)r->w * r->h > 400000ll;
-  const bool serial_marches = true;  // (two replicas: their marches one after the other)
+  const bool plan_on_maps = !sharded && !deferred && (long long)r->w * r->h > 400000ll;
   std::vector<const float *> fusion_ptr((size_t)n, nullptr);
   r->ran = true; r->last_caller = cur;
   if (r->timeline) {
@@ -307,7 +272,6 @@ static int runner_run_impl(svoslam_runner *r, const uint16_t *const *d_depths, c
   hipStream_t all[5] = {r->s_maps, r->s_track, r->s_prep, r->s_map[0], r->s_map[1]};
   for (hipStream_t s : all) SVO_HIP(hipStreamWaitEvent(s, r->ev_begin, 0));
 
-  const bool staged = svoslam::config().graphs != 0;  // graphs are keyed on pointers: frames are staged through fixed buffers
   // frame-sharded ranks that march at most one frame in three plan on the map stream (see enqueue_commit)
   bool plan_on_map = false;
   // ... or, by default, run the STRUCTURE CHAIN (svoslam_svo_fuse_plan_structure): a plan reads structure words only, so
@@ -321,7 +285,7 @@ static int runner_run_impl(svoslam_runner *r, const uint16_t *const *d_depths, c
     int marched = 0;
     for (int i = 0; i < n; i++) marched += march[i] ? 1 : 0;
     plan_on_map = 3 * marched <= n;
-    if (plan_on_map && R == 1 && !deferred) { chain = true; plan_on_map = false; }
+    if (plan_on_map && !deferred) { chain = true; plan_on_map = false; }
   }
   if (chain) SVO_TRY(svoslam_pool_structure_begin(r->pool, r->s_prep));
   hipStream_t s_maps = r->s_maps;
@@ -329,11 +293,8 @@ static int runner_run_impl(svoslam_runner *r, const uint16_t *const *d_depths, c
     if (sharded) return SVOSLAM_OK;  // tracked elsewhere: this camera only composes poses
     if (i >= 2) SVO_HIP(hipStreamWaitEvent(s_maps, ev_pose[i - 2], 0));  // its map set was the "last" set of frame i-2
     mark(i, 0, s_maps);
-    // fixed input addresses only where the library replays recorded launch sequences (graphs are keyed on pointers);
-    // the caller's frames stay valid for the whole call (its stream is joined at the end)
-    if (staged) SVO_HIP(hipMemcpyAsync(r->in_track, d_depths[i], px * 2, hipMemcpyDeviceToDevice, s_maps));
     int32_t used = 0;
-    SVO_TRY(svoslam_camera_prepare(r->cam, staged ? r->in_track : d_depths[i], d_rgbs[i], timestamps[i], &used, s_maps));
+    SVO_TRY(svoslam_camera_prepare(r->cam, d_depths[i], d_rgbs[i], timestamps[i], &used, s_maps));
     if (!used) return SVOSLAM_ERR_INVALID_ARG;  // cannot happen after the validation above
     SVO_HIP(hipEventRecord(ev_maps[i], s_maps));
     mark(i, 1, s_maps);
@@ -366,24 +327,20 @@ static int runner_run_impl(svoslam_runner *r, const uint16_t *const *d_depths, c
     // drops from 5450 to 3500 frames/s -- six busy streams on the runtime's hardware queues.)
     hipStream_t s_sort = chain ? r->s_maps : r->s_prep;
     SVO_HIP(hipStreamWaitEvent(s_sort, ev_pose[i], 0));
-    if (i >= kRing)  // the ring slot's previous user: both of its commits are done with workspace, points and colours
-      for (int k = 0; k < R; k++) SVO_HIP(hipStreamWaitEvent(s_sort, ev_commit[k][i - kRing], 0));
+    if (i >= kRing)  // the ring slot's previous user: its commit is done with workspace and points
+      SVO_HIP(hipStreamWaitEvent(s_sort, ev_commit[0][i - kRing], 0));
     mark(i, 4, s_sort);
-    if (staged) {
-      SVO_HIP(hipMemcpyAsync(r->in_prep, d_depths[i], px * 2, hipMemcpyDeviceToDevice, s_sort));
-      SVO_HIP(hipMemcpyAsync(r->in_rgb[i % kRing], d_rgbs[i], px * 3, hipMemcpyDeviceToDevice, s_sort));
-    }
     if (presorted) {
       if (sorted_events && sorted_events[i]) SVO_HIP(hipStreamWaitEvent(s_sort, reinterpret_cast<hipEvent_t>(sorted_events[i]), 0));
       SVO_TRY(svoslam_svo_fuse_adopt_sorted(ws, d_sorted_keys[i], d_sorted_idx[i], npts, r->depth));
       SVO_HIP(hipEventRecord(ev_bp[i], s_sort));
     } else if (r->fused_front) {
       // main.cpp:39-44 + computeKeys in one launch, no point cloud in memory (svoslam_svo_fuse_sort_frame), then the sort
-      SVO_TRY(svoslam_svo_fuse_sort_frame(ws, staged ? r->in_prep : d_depths[i], fusion_ptr[i], r->w, r->h, r->fx, r->fy, r->depth,
+      SVO_TRY(svoslam_svo_fuse_sort_frame(ws, d_depths[i], fusion_ptr[i], r->w, r->h, r->fx, r->fy, r->depth,
                                           r->center, r->edge, r->bbox, s_sort));
       SVO_HIP(hipEventRecord(ev_bp[i], s_sort));
     } else {
-      SVO_TRY(svoslam_generate_vertex_map(staged ? r->in_prep : d_depths[i], pts, r->w, r->h, r->fx, r->fy, r->w, r->h, s_sort));  // main.cpp:39
+      SVO_TRY(svoslam_generate_vertex_map(d_depths[i], pts, r->w, r->h, r->fx, r->fy, r->w, r->h, s_sort));  // main.cpp:39
       SVO_TRY(svoslam_transform_vertex_map_dmat(pts, fusion_ptr[i], npts, s_sort));                         // main.cpp:40-41
       SVO_TRY(svoslam_point_cloud_bbox_device(r->ws[0], pts, npts, r->bbox, s_sort));                       // main.cpp:44
       SVO_HIP(hipEventRecord(ev_bp[i], s_sort));
@@ -404,49 +361,40 @@ static int runner_run_impl(svoslam_runner *r, const uint16_t *const *d_depths, c
       mark(i, 6, s_plan);
       return SVOSLAM_OK;
     }
-    // the plan reads the replica that receives commit i-1 FIRST (the one frame i-1 is marched on); the march only reads
-    const int src = i > 0 ? ((i - 1) & (R - 1)) : 0;
+    // the plan reads the tree commit i-1 leaves; the march only reads
     if (plan_on_maps) {  // (see above)
       SVO_HIP(hipEventRecord(ev_sorted[i], r->s_prep));
       s_plan = r->s_maps;
       SVO_HIP(hipStreamWaitEvent(s_plan, ev_sorted[i], 0));
     }
-    if (i > 0) SVO_HIP(hipStreamWaitEvent(s_plan, ev_commit[src][i - 1], 0));
+    if (i > 0) SVO_HIP(hipStreamWaitEvent(s_plan, ev_commit[0][i - 1], 0));
     mark(i, 5, s_plan);
-    svoslam_pool *planned = replica(r, src);
-    const int32_t cap_before = planned->capacity;
-    SVO_TRY(svoslam_svo_fuse_plan(ws, npts, r->depth, planned, s_plan));
-    if (R == 2 && planned->capacity != cap_before) {
-      // the plan had to grow its replica (it waited for the whole device to do so): the other one follows
-      svoslam_pool *other = replica(r, src ^ 1);
-      SVO_HIP(hipDeviceSynchronize());
-      SVO_TRY(svoslam_pool_reserve(other, planned->capacity, r->s_prep));
-    }
+    SVO_TRY(svoslam_svo_fuse_plan(ws, npts, r->depth, r->pool, s_plan));
     // the child tiles of this frame's splits, beyond the pool's size, while the previous frame is still being marched:
     // the commit on the map stream -- the stream that bounds the frame -- is then two launches instead of three
-    if (R == 1 && !deferred && r->early_split) SVO_TRY(svoslam_svo_fuse_split_early(ws, npts, r->depth, planned, s_plan));
+    if (!deferred && r->early_split) SVO_TRY(svoslam_svo_fuse_split_early(ws, npts, r->depth, r->pool, s_plan));
     SVO_HIP(hipEventRecord(ev_plan[i], s_plan));
     mark(i, 6, s_plan);
     return SVOSLAM_OK;
   };
-  auto enqueue_commit = [&](int i, int k, bool last) -> int {
-    SVO_HIP(hipStreamWaitEvent(r->s_map[k], ev_plan[i], 0));
+  hipStream_t s_map = r->s_map[0];
+  auto enqueue_commit = [&](int i) -> int {
+    SVO_HIP(hipStreamWaitEvent(s_map, ev_plan[i], 0));
     if (plan_on_map) {
       // Frame-sharded ranks march one frame in N: the map stream has room, and the stream that back-projects and sorts
       // is what bounds the frame (0.145 + 0.045 ms at cfg3).  The plan -- which needs commit i-1 anyway -- runs HERE, in
       // order behind that commit, and S goes straight on to the next frame's sort: 4440 -> 5240 frames/s for a rank of 8,
       // 3870 -> 4280 for a rank of 4 (a rank of 2 marches every other frame and loses 2 %: it keeps the plan on S).
-      mark(i, 6, r->s_map[k]);  // (plan begin; mark 5 = sort end)
-      SVO_TRY(svoslam_svo_fuse_plan(r->ws[i % kRing], npts, r->depth, r->pool, r->s_map[k]));
+      mark(i, 6, s_map);  // (plan begin; mark 5 = sort end)
+      SVO_TRY(svoslam_svo_fuse_plan(r->ws[i % kRing], npts, r->depth, r->pool, s_map));
     }
-    if (k == (i & (R - 1))) mark(i, 7, r->s_map[k]);
-    SVO_TRY(svoslam_svo_fuse_commit_to(r->ws[i % kRing], staged ? r->in_rgb[i % kRing] : d_rgbs[i], npts, r->depth, replica(r, k), k,
-                                       last ? 0 : 1, r->s_map[k]));
-    SVO_HIP(hipEventRecord(ev_commit[k][i], r->s_map[k]));
-    if (k == (i & (R - 1))) mark(i, 8, r->s_map[k]);
+    mark(i, 7, s_map);
+    SVO_TRY(svoslam_svo_fuse_commit(r->ws[i % kRing], d_rgbs[i], npts, r->depth, r->pool, s_map));
+    SVO_HIP(hipEventRecord(ev_commit[0][i], s_map));
+    mark(i, 8, s_map);
     return SVOSLAM_OK;
   };
-  // One replica, deferred commits (the default for images up to 640x480-class, svoslam_runner::deferred): stream C computes the commit of frame k+1 -- splits, leaf
+  // Deferred commits (the default for images up to 640x480-class, svoslam_runner::deferred): stream C computes the commit of frame k+1 -- splits, leaf
   // blends, mip levels, into memory the march cannot see (svoslam_svo_fuse_commit_deferred) -- WHILE stream M ray-marches
   // frame k; M then publishes it with one short launch (svoslam_svo_fuse_apply) and marches frame k+1.  The map stream
   // carries apply + grid / brick refresh + march instead of commit + refresh + march.  Round 2, beside the tree march (a
@@ -462,15 +410,15 @@ static int runner_run_impl(svoslam_runner *r, const uint16_t *const *d_depths, c
     // (the plan of frame i HERE, in order ahead of its commit and behind apply(i-1) -- one hand-off between streams less in the
     // cycle -- was measured: 2000-2200 frames/s against 2030-2390, the sorts then run unthrottled beside the march: not kept)
     mark(i, 7, s_compute);
-    SVO_TRY(svoslam_svo_fuse_commit_deferred(r->ws[i % kRing], staged ? r->in_rgb[i % kRing] : d_rgbs[i], npts, r->depth, r->pool, s_compute));
+    SVO_TRY(svoslam_svo_fuse_commit_deferred(r->ws[i % kRing], d_rgbs[i], npts, r->depth, r->pool, s_compute));
     SVO_HIP(hipEventRecord(ev_commit[1][i], s_compute));
     return SVOSLAM_OK;
   };
   auto enqueue_apply = [&](int i) -> int {
-    SVO_HIP(hipStreamWaitEvent(r->s_map[0], ev_commit[1][i], 0));
-    SVO_TRY(svoslam_svo_fuse_apply(r->ws[i % kRing], r->pool, r->s_map[0]));
-    SVO_HIP(hipEventRecord(ev_commit[0][i], r->s_map[0]));
-    mark(i, 8, r->s_map[0]);
+    SVO_HIP(hipStreamWaitEvent(s_map, ev_commit[1][i], 0));
+    SVO_TRY(svoslam_svo_fuse_apply(r->ws[i % kRing], r->pool, s_map));
+    SVO_HIP(hipEventRecord(ev_commit[0][i], s_map));
+    mark(i, 8, s_map);
     return SVOSLAM_OK;
   };
   auto enqueue_all_deferred = [&]() -> int {
@@ -494,16 +442,16 @@ static int runner_run_impl(svoslam_runner *r, const uint16_t *const *d_depths, c
         SVO_TRY(enqueue_compute(i + 1));  // host order: BEFORE the march of frame i, whose grid refresh must leave this commit's marks alone
       }
       if (!march || march[i]) {
-        uint8_t *img = d_images ? d_images[i] : ((i == n - 1) ? d_image : r->scratch_image[0]);
+        uint8_t *img = d_images ? d_images[i] : ((i == n - 1) ? d_image : r->scratch_image);
         SVO_TRY(svoslam_cone_trace_svo_band(img, r->w, r->h, row_first, rows, r->fov, views + 16 * (size_t)i, r->pool->d_data,
-                                            r->center, r->edge, r->mode, d_steps, r->s_map[0]));
+                                            r->center, r->edge, r->mode, d_steps, s_map));
       }
-      mark(i, 9, r->s_map[0]);
+      mark(i, 9, s_map);
     }
     return SVOSLAM_OK;
   };
   auto enqueue_all = [&]() -> int {
-    if (R == 1 && deferred) return enqueue_all_deferred();
+    if (deferred) return enqueue_all_deferred();
     SVO_TRY(enqueue_maps(0));
     SVO_TRY(enqueue_track(0));
     if (n > 1) SVO_TRY(enqueue_maps(1));
@@ -511,7 +459,6 @@ static int runner_run_impl(svoslam_runner *r, const uint16_t *const *d_depths, c
     for (int i = 0; i < n; i++) {
       if (i + 1 < n) SVO_TRY(enqueue_track(i + 1));
       if (i + 2 < n) SVO_TRY(enqueue_maps(i + 2));  // (one stream: behind track i+1, ahead of track i+2 -- two map sets ahead at most)
-      const int a = i & (R - 1);  // the replica frame i is marched on: it gets commit i first
       // The host stays at most `lead` commits ahead of the device (default 2; svoslam_config.runner_lead = 0: as far as the
       // pool's size ring allows, 8).  Whatever has been enqueued when the host STOPS enqueuing drains at 0.6 ms per
       // frame instead of 0.32 (measured with HIP events per stage: the kernels themselves keep their durations and the
@@ -519,21 +466,17 @@ static int runner_run_impl(svoslam_runner *r, const uint16_t *const *d_depths, c
       // steady state).  With a lead of 8 frames that tail was 8 of the 20 frames of a short call: 2130 -> 2580 frames/s.
       // (a rank of 8, lead 1 / 2: 4480 / 5030 frames/s)
       const int lead = r->lead < 0 ? 2 : r->lead;
-      if (lead > 0 && i >= lead) SVO_HIP(hipEventSynchronize(ev_commit[a][i - lead]));
-      SVO_TRY(enqueue_commit(i, a, R == 1));
-      if (i + 1 < n && !chain) SVO_TRY(enqueue_prepare(i + 1));  // host order: after ev_commit[a][i] has been recorded
-      // one march at a time: two of them (1200 workgroups) leave no CU for the tracker's and the fusion's workgroups
-      if (R == 2 && serial_marches && i > 0) SVO_HIP(hipStreamWaitEvent(r->s_map[a], ev_ray[i - 1], 0));
+      if (lead > 0 && i >= lead) SVO_HIP(hipEventSynchronize(ev_commit[0][i - lead]));
+      SVO_TRY(enqueue_commit(i));
+      if (i + 1 < n && !chain) SVO_TRY(enqueue_prepare(i + 1));  // host order: after ev_commit[0][i] has been recorded
       if (!march || march[i]) {
-        uint8_t *img = d_images ? d_images[i] : ((i == n - 1) ? d_image : r->scratch_image[a]);
-        SVO_TRY(svoslam_cone_trace_svo_band(img, r->w, r->h, row_first, rows, r->fov, views + 16 * (size_t)i, replica(r, a)->d_data,
-                                            r->center, r->edge, r->mode, d_steps, r->s_map[a]));
-        if (chain) { SVO_HIP(hipEventRecord(ev_ray[i], r->s_map[a])); last_march = i; }
+        uint8_t *img = d_images ? d_images[i] : ((i == n - 1) ? d_image : r->scratch_image);
+        SVO_TRY(svoslam_cone_trace_svo_band(img, r->w, r->h, row_first, rows, r->fov, views + 16 * (size_t)i, r->pool->d_data,
+                                            r->center, r->edge, r->mode, d_steps, s_map));
+        if (chain) { SVO_HIP(hipEventRecord(ev_ray[i], s_map)); last_march = i; }
       }
-      if (R == 2) SVO_HIP(hipEventRecord(ev_ray[i], r->s_map[a]));
-      mark(i, 9, r->s_map[a]);
+      mark(i, 9, s_map);
       if (i + 1 < n && chain) SVO_TRY(enqueue_prepare(i + 1));  // host order: after the march's event, which its plan may have to wait for
-      if (R == 2) SVO_TRY(enqueue_commit(i, a ^ 1, true));  // behind the march of frame i-1 on that replica
     }
     return SVOSLAM_OK;
   };
@@ -603,7 +546,6 @@ int svoslam_runner_run_model(svoslam_runner *r, const uint16_t *const *d_depths,
   if (models_used) *models_used = 0;
   if (!r || n < 0 || (n > 0 && (!d_depths || !d_rgbs || !timestamps || !views || !d_image))) return SVOSLAM_ERR_INVALID_ARG;
   if (row_first < 0 || rows < 0 || row_first + rows > r->h || !(min_coverage >= 0.0f)) return SVOSLAM_ERR_INVALID_ARG;
-  if (r->replicas != 1) return SVOSLAM_ERR_INVALID_ARG;
   for (int i = 0; i < n; i++) if (!d_depths[i] || !d_rgbs[i] || (i > 0 && timestamps[i] <= timestamps[i - 1])) return SVOSLAM_ERR_INVALID_ARG;
   if (n == 0) return SVOSLAM_OK;
   hipStream_t s = reinterpret_cast<hipStream_t>(caller_stream);
@@ -655,7 +597,7 @@ int svoslam_runner_run_model(svoslam_runner *r, const uint16_t *const *d_depths,
     } else {
       SVO_TRY(svoslam_camera_set_model_depth(r->cam, nullptr, s));
     }
-    SVO_TRY(svoslam_cone_trace_svo_band(i == n - 1 ? d_image : r->scratch_image[0], r->w, r->h, row_first, rows, r->fov, views + 16 * (size_t)i,
+    SVO_TRY(svoslam_cone_trace_svo_band(i == n - 1 ? d_image : r->scratch_image, r->w, r->h, row_first, rows, r->fov, views + 16 * (size_t)i,
                                         r->pool->d_data, r->center, r->edge, r->mode, d_steps, s));
   }
   if (models_used) *models_used = used_models;

@@ -1326,7 +1326,7 @@ int pool_expand(svoslam_pool *pool, float center[3], float *edge, const float to
   return SVOSLAM_OK;
 }
 
-// back to initOctree (8 zeroed root children) keeping the allocation, so recorded launch graphs stay valid.  Blocking.
+// back to initOctree (8 zeroed root children) keeping the allocation.  Blocking.
 int pool_reset(svoslam_pool *pool, hipStream_t stream) {
   if (!pool || !pool->d_data) return SVOSLAM_ERR_INVALID_ARG;
   SVO_HIP(hipDeviceSynchronize());
@@ -1477,7 +1477,7 @@ static inline PlanCounts *small_counts(svoslam_workspace *ws) { return reinterpr
 static inline int *small_any(svoslam_workspace *ws) { return reinterpret_cast<int *>(ws->small.as<u32>() + 640); }
 static inline u32 *small_n0(svoslam_workspace *ws) { return ws->small.as<u32>() + 648; }  // deferred commit: first new tile
 static inline unsigned *small_ticket(svoslam_workspace *ws) { return ws->small.as<u32>() + 656; }  // plan_scan_finish_kernel's arrival count
-static inline unsigned *small_strad_ticket(svoslam_workspace *ws, int slot) { return ws->small.as<u32>() + 664 + 8 * slot; }  // mip_straddle2_kernel's (zero between launches)
+static inline unsigned *small_strad_ticket(svoslam_workspace *ws) { return ws->small.as<u32>() + 664; }  // mip_straddle2_kernel's (zero between launches)
 
 // keys of the n inputs are in ws->keys_a
 // The blocking insert's sort (round 5): one packed word per point where key and index fit 64 bits -- and the key ALONE on the
@@ -1656,7 +1656,8 @@ static int fuse_sort_impl(svoslam_workspace *ws, const float *d_points, const Fr
     }
   }
   u64 *skey = nullptr; u32 *sidx = nullptr;
-  auto enqueue = [&]() -> int {
+  {
+    StageScope timed(kStageFuseSort, stream);
     if (packed) {
       const int bits0 = radix_packed_first_bits(key_bits);
       if (fs)
@@ -1672,19 +1673,6 @@ static int fuse_sort_impl(svoslam_workspace *ws, const float *d_points, const Fr
       SVO_TRY(radix_sort_pairs(ws, n, key_bits, stream, &skey, &sidx));
     }
     SVO_LAUNCH_CHECK();
-    return SVOSLAM_OK;
-  };
-  GraphKey key;
-  key.add(fs ? (const void *)fs->depth : (const void *)d_points).add((unsigned long long)n).add((unsigned long long)depth)
-     .addf(center[0]).addf(center[1]).addf(center[2]).addf(edge).add(ws->layout_hash()).add(fs ? fs->pose : nullptr).add(d_bbox7)
-     .add(ws->frame_bbox.ptr).add((unsigned long long)(fs ? fs->first : 0));
-  {
-    StageScope timed(kStageFuseSort, stream);
-    SVO_TRY(ws->g_sort.run(key, stream, enqueue));
-  }
-  if (!skey) {  // replayed: where the recorded sort leaves its result
-    if (packed) SVO_TRY(radix_sort_packed_output(ws, key_bits, &skey, &sidx));
-    else SVO_TRY(radix_sort_output(ws, n, key_bits, &skey, &sidx));
   }
   ws->sorted_keys = skey; ws->sorted_idx = sidx;
   return SVOSLAM_OK;
@@ -1825,7 +1813,8 @@ static int fuse_plan_impl(svoslam_workspace *ws, int n, int depth, svoslam_pool 
   int *d_struct = structure ? tracker_of(pool)->d_struct : nullptr;
   int split_blocks = (int)cdiv(rmax, 256);
   if (split_blocks > 2048) split_blocks = 2048;
-  auto enqueue = [&]() -> int {  // three launches (round 1: a memset and five)
+  {  // three launches (round 1: a memset and five)
+    StageScope timed(kStageFusePlan, stream);
     plan_count_kernel<<<xcd_grid(tiles), kPlanThreads, 0, stream>>>(skey, n, depth, pool->d_data, leaf_t, leaf_f, ws->leaf_start.as<u32>(), tile_hist, tiles, small_any(ws));
     plan_scan_finish_kernel<<<256, 256, 0, stream>>>(tile_hist, tiles, small_totals(ws), small_ticket(ws), small_bucket_base(ws),
                                                      small_counts(ws), small_any(ws), d_struct, small_n0(ws));
@@ -1837,14 +1826,6 @@ static int fuse_plan_impl(svoslam_workspace *ws, int n, int depth, svoslam_pool 
                                                          small_bucket_base(ws), small_counts(ws), pool->d_data, pool->d_size, depth, nullptr,
                                                          small_n0(ws), 1);
     SVO_LAUNCH_CHECK();
-    return SVOSLAM_OK;
-  };
-  GraphKey key;
-  key.add(skey).add((unsigned long long)n).add((unsigned long long)depth).add(pool->d_data).add(ws->layout_hash())
-     .add((unsigned long long)structure).add(d_struct);
-  {
-    StageScope timed(kStageFusePlan, stream);
-    SVO_TRY(ws->g_plan.run(key, stream, enqueue));
   }
   ws->planned_n = n;
   ws->planned_pool = pool;
@@ -1860,10 +1841,6 @@ int svo_fuse_plan_structure(svoslam_workspace *ws, int n, int depth, svoslam_poo
   return fuse_plan_impl(ws, n, depth, pool, true, stream);
 }
 
-// Applies the planned commit to `pool`.  slot / keep_plan serve callers that keep several byte-identical replicas of
-// one map (the frame scheduler ray-marches one replica while the next frame is committed to the other): the same plan
-// -- made against ANY of the replicas in the state before this commit -- is applied to each of them, every
-// application with its own slot (0 or 1: the scratch list of the mip pass) and all but the last with keep_plan.
 // The part of the next commit that no ray march can see, ahead of the commit: the child tiles of the planned splits are
 // initialised beyond the pool's present size (split_all_kernel without its links and without its level-grid marks) while the
 // previous frame is still being ray-marched.  The commit that follows on this workspace and pool then runs two launches
@@ -1891,17 +1868,17 @@ int svo_fuse_split_early(svoslam_workspace *ws, int n, int depth, svoslam_pool *
 // keyrange (key-range sharded commit, below): a deferred commit of this rank's slice of the frame -- the workspace's sorted arrays hold the
 // slice followed by padding, *n_live its length --, without marks for the ray march's grid / bricks (keyrange_mark_kernel makes them, from
 // ALL keys), without the pool's new size and without the size readback (svo_fuse_keyrange_apply: keyrange_finish_kernel, tracker_push)
-static int commit_impl(svoslam_workspace *ws, const uint8_t *d_colors, int n, int depth, svoslam_pool *pool, int slot,
-                       bool keep_plan, bool deferred, hipStream_t stream, const int *n_live = nullptr) {
+static int commit_impl(svoslam_workspace *ws, const uint8_t *d_colors, int n, int depth, svoslam_pool *pool, bool deferred,
+                       hipStream_t stream, const int *n_live = nullptr) {
   const bool keyrange = n_live != nullptr;
-  if (!ws || !pool || n < 0 || (n > 0 && !d_colors) || slot < 0 || slot > 1) return SVOSLAM_ERR_INVALID_ARG;
+  if (!ws || !pool || n < 0 || (n > 0 && !d_colors)) return SVOSLAM_ERR_INVALID_ARG;
   if (pool_shadow_pending(pool)) return SVOSLAM_ERR_INVALID_ARG;  // a deferred commit of this pool has not been applied
   if (depth < 1 || depth > SVOSLAM_MAX_DEPTH) return SVOSLAM_ERR_DEPTH;
   if (ws->planned_n != n) return SVOSLAM_ERR_INVALID_ARG;  // svo_fuse_plan has not run for this batch
-  if (!keep_plan) ws->planned_n = -1;
+  ws->planned_n = -1;
   ws->deferred_pool = nullptr;
   const bool early = ws->early_split_pool != nullptr;
-  if (early && (ws->early_split_pool != pool || deferred || keep_plan)) return SVOSLAM_ERR_INVALID_ARG;  // one pool, direct commit
+  if (early && (ws->early_split_pool != pool || deferred)) return SVOSLAM_ERR_INVALID_ARG;  // one pool, direct commit
   ws->early_split_pool = nullptr;
   if (ws->structure_planned) {
     ws->structure_planned = false;
@@ -1926,12 +1903,11 @@ static int commit_impl(svoslam_workspace *ws, const uint8_t *d_colors, int n, in
   int split_blocks = (int)cdiv(rmax, 256);
   if (split_blocks > 2048) split_blocks = 2048;
   const int fill_tiles = (int)cdiv(n, kFillThreads);
-  DeviceBuffer &sb = slot == 0 ? ws->strad : ws->strad_b;
   // [level][tile] straddler entries | per-tile boundary records | [level][group] super straddlers (mip_straddle2_kernel)
   const int strad_groups = (int)cdiv(fill_tiles, kStradGroup);
   const size_t strad_words = (size_t)(SVOSLAM_MAX_DEPTH + 1) * (size_t)fill_tiles * 2, bc_words = 2 * (size_t)fill_tiles;
-  SVO_TRY(sb.reserve((strad_words + bc_words + (size_t)(SVOSLAM_MAX_DEPTH + 1) * (size_t)strad_groups * 2) * 4));
-  u32 *strad = sb.as<u32>();
+  SVO_TRY(ws->strad.reserve((strad_words + bc_words + (size_t)(SVOSLAM_MAX_DEPTH + 1) * (size_t)strad_groups * 2) * 4));
+  u32 *strad = ws->strad.as<u32>();
   int *strad_bc = reinterpret_cast<int *>(strad + strad_words);
   u32 *sstrad = strad + strad_words + bc_words;
   const bool two_tier = !deferred;  // (deferred commits keep the single-workgroup straddler pass: its list doubles as the apply list)
@@ -1949,7 +1925,8 @@ static int commit_impl(svoslam_workspace *ws, const uint8_t *d_colors, int n, in
   SVO_TRY(tracker_make_room(pool));
   int brick_shift = -1;
   u32 *grid_dirty = keyrange ? nullptr : pool_accel_dirty_bitmap(pool, deferred ? (int)(epoch & 1u) : 0, depth, &brick_shift);  // nullptr: not a registered pool
-  auto enqueue = [&]() -> int {
+  {
+    StageScope timed(kStageFuseCommit, stream);
     if (!early)
       split_all_kernel<<<split_blocks, 256, 0, stream>>>(ws->rec_key.as<u64>(), ws->rec_front.as<u32>(),
                                                          ws->rec_pass.as<unsigned char>(), small_bucket_base(ws), small_counts(ws),
@@ -1963,43 +1940,21 @@ static int commit_impl(svoslam_workspace *ws, const uint8_t *d_colors, int n, in
                                                                    small_bucket_base(ws), small_n0(ws), early ? ws->leaf_rec0.as<u32>() : nullptr, leaf_start,
                                                                    two_tier ? strad_bc : nullptr, brick_shift, n_live);
     if (two_tier)
-      mip_straddle2_kernel<<<strad_groups, kStrad2Threads, 0, stream>>>(pool->d_data, strad, strad_bc, sstrad, small_strad_ticket(ws, slot), fill_tiles,
+      mip_straddle2_kernel<<<strad_groups, kStrad2Threads, 0, stream>>>(pool->d_data, strad, strad_bc, sstrad, small_strad_ticket(ws), fill_tiles,
                                                                         depth, small_counts(ws), pool->d_size, grid_dirty,
                                                                         trk ? trk->h_size : nullptr, trk ? trk->d_slot : nullptr);
     else
       mip_straddle_kernel<<<1, kStradThreads, 0, stream>>>(pool->d_data, strad, fill_tiles, depth, small_counts(ws), pool->d_size, grid_dirty,
                                                            trk ? trk->h_size : nullptr, trk ? trk->d_slot : nullptr, shadow, epoch, keyrange ? 1 : 0, n_live);
     SVO_LAUNCH_CHECK();
-    return SVOSLAM_OK;
-  };
-  if (deferred) {  // the epoch changes with every call: not a recorded sequence
-    {
-      StageScope timed(kStageFuseCommit, stream);
-      SVO_TRY(enqueue());
-    }
-    if (keyrange) { ws->keyrange_bound = 8 * rmax; return SVOSLAM_OK; }
-    pool->pending += 1;
-    return tracker_push(pool, 8 * rmax, stream);
   }
-  GraphKey key;
-  key.add(skey).add(d_colors).add((unsigned long long)n).add((unsigned long long)depth).add(pool->d_data).add(pool->d_size)
-     .add((unsigned long long)slot).add(grid_dirty).add(trk ? (const void *)trk->h_size : nullptr).add(ws->layout_hash())
-     .add((unsigned long long)early).add((unsigned long long)(brick_shift + 1));
-  {
-    StageScope timed(kStageFuseCommit, stream);
-    SVO_TRY(ws->g_commit.run(key, stream, enqueue));
-  }
+  if (keyrange) { ws->keyrange_bound = 8 * rmax; return SVOSLAM_OK; }
   pool->pending += 1;
   return tracker_push(pool, 8 * rmax, stream);
 }
 
-int svo_fuse_commit_to(svoslam_workspace *ws, const uint8_t *d_colors, int n, int depth, svoslam_pool *pool, int slot,
-                       bool keep_plan, hipStream_t stream) {
-  return commit_impl(ws, d_colors, n, depth, pool, slot, keep_plan, false, stream);
-}
-
 int svo_fuse_commit(svoslam_workspace *ws, const uint8_t *d_colors, int n, int depth, svoslam_pool *pool, hipStream_t stream) {
-  return commit_impl(ws, d_colors, n, depth, pool, 0, false, false, stream);
+  return commit_impl(ws, d_colors, n, depth, pool, false, stream);
 }
 
 // Deferred commit: the commit's whole computation (splits, leaf blends, mip levels) WITHOUT a single store a ray march
@@ -2009,7 +1964,7 @@ int svo_fuse_commit(svoslam_workspace *ws, const uint8_t *d_colors, int n, int d
 // pool must not be read by anything that expects the new state, nor written, in between.  Same final pool contents as
 // svo_fuse_commit.  Used by the frame scheduler: its map stream carries apply + march instead of commit + march.
 int svo_fuse_commit_deferred(svoslam_workspace *ws, const uint8_t *d_colors, int n, int depth, svoslam_pool *pool, hipStream_t stream) {
-  return commit_impl(ws, d_colors, n, depth, pool, 0, false, true, stream);
+  return commit_impl(ws, d_colors, n, depth, pool, true, stream);
 }
 
 int svo_fuse_apply(svoslam_workspace *ws, svoslam_pool *pool, hipStream_t stream) {
@@ -2599,7 +2554,7 @@ int svo_fuse_keyrange_commit(svoslam_workspace *ws, const unsigned long long *d_
   SVO_LAUNCH_CHECK();
   SVO_TRY(svo_fuse_adopt_sorted(ws, ws->kr_keys.as<u64>(), ws->kr_idx.as<u32>(), n, depth));
   SVO_TRY(svo_fuse_plan(ws, n, depth, pool, stream));
-  SVO_TRY(commit_impl(ws, d_colors, n, depth, pool, 0, false, true, stream, win + 2));
+  SVO_TRY(commit_impl(ws, d_colors, n, depth, pool, true, stream, win + 2));
   // the delta
   unsigned long long *shadow = nullptr;
   u32 epoch = 0;

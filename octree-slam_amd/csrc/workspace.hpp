@@ -5,7 +5,6 @@
 #pragma once
 
 #include "common.hpp"
-#include "graph_cache.hpp"
 
 namespace svoslam {
 
@@ -47,7 +46,6 @@ struct svoslam_workspace {
   svoslam::DeviceBuffer leaf_start;                       // async path: per sorted key, child tile where the commit's walk resumes the plan's
   svoslam::DeviceBuffer path_nodes;                       // [(D-1)][n] node index per owned depth (mip lists)
   svoslam::DeviceBuffer strad;                            // [D][tiles][2] nodes whose leaf run crosses a workgroup (async commit)
-  svoslam::DeviceBuffer strad_b;                          // the same for the commit of the plan to a second replica of the pool
   svoslam::DeviceBuffer kr_keys, kr_idx, kr_small;        // key-range sharded commit: the rank's slice of the sorted arrays; window, numbering table, scalars
   const void *keyrange_pool = nullptr;                    // ... svo_fuse_keyrange_commit has run for this pool, svo_fuse_keyrange_apply is due
   svoslam::DeviceBuffer apply_nodes;                      // deferred commit: per fill tile, the nodes its workgroup wrote (dense from the tile's start; counts behind the lists)
@@ -68,7 +66,6 @@ struct svoslam_workspace {
   bool structure_planned = false;                          // ... by svo_fuse_plan_structure (its reservation is released by its commit)
   long long keyrange_bound = 0;                            // key-range commit: the plan's reservation, released by svo_fuse_keyrange_apply's size readback
   const void *planned_pool = nullptr;                      // the pool svo_fuse_plan read (its reservation is already booked)
-  svoslam::GraphCache g_sort, g_plan, g_commit;            // recorded launch sequences of the three phases
   // `small` (4 KB of totals / bases / counters) is zeroed when it is created: the planner's any_valid word and arrival
   // ticket must start at zero (every plan leaves them at zero).  Blocking, once per workspace.
   int reserve_small() {
@@ -77,20 +74,11 @@ struct svoslam_workspace {
     SVO_HIP(svoslam::memset_sync(small.ptr, 0, small.bytes));
     return SVOSLAM_OK;
   }
-  // every buffer address the recorded phases bake in (a reallocation makes a new key)
-  unsigned long long layout_hash() const {
-    const void *p[] = {keys_a.ptr, keys_b.ptr, vals_a.ptr, vals_b.ptr, tile_hist.ptr, small.ptr, leaf_t.ptr, leaf_f.ptr,
-                       rec_key.ptr, rec_front.ptr, rec_pass.ptr, path_nodes.ptr, strad.ptr, strad_b.ptr, apply_nodes.ptr, leaf_rec0.ptr, leaf_start.ptr};
-    unsigned long long h = 1469598103934665603ull;
-    for (const void *q : p) h = (h ^ (unsigned long long)(uintptr_t)q) * 1099511628211ull;
-    return h;
-  }
   void release_all() {
     keys_a.release(); keys_b.release(); vals_a.release(); vals_b.release(); tile_hist.release(); small.release();
-    leaf_t.release(); leaf_f.release(); rec_key.release(); rec_front.release(); path_nodes.release(); strad.release(); strad_b.release();
+    leaf_t.release(); leaf_f.release(); rec_key.release(); rec_front.release(); path_nodes.release(); strad.release();
     rec_pass.release(); apply_nodes.release(); leaf_rec0.release(); leaf_start.release();
     bfs_a.release(); bfs_b.release(); bfs_mask.release(); bfs_ptr.release(); misc.release(); scan_tmp.release(); frame_bbox.release();
     if (h_counts) { (void)hipHostFree(h_counts); h_counts = nullptr; }
-    g_sort.clear(); g_plan.clear(); g_commit.clear();
   }
 };

@@ -394,7 +394,7 @@ class SlamPipeline:
         return self.model_depth
 
     def reset(self):
-        """empty map and a fresh tracker; allocations, streams and the launch graphs recorded so far are kept"""
+        """empty map and a fresh tracker; allocations and streams are kept"""
         self.pool.reset()
         self.cam.reset()
         if self.frame_sharded:
@@ -539,11 +539,6 @@ class SlamPipeline:
             self._s_prep, self._s_map = torch.cuda.Stream(), torch.cuda.Stream()
             self._ws2 = [self.ws, pkg.Workspace()]
             self._points2 = [self.points, torch.empty_like(self.points)]
-            # fixed input addresses per stream: the library replays its launch sequences as HIP graphs keyed
-            # on the pointers it is given (csrc/graph_cache.hpp), so each frame is copied into a staging buffer
-            self._in_track = torch.empty_like(depths[0])
-            self._in_prep = torch.empty_like(depths[0])
-            self._in_rgb = torch.empty_like(rgbs[0])
         cur = torch.cuda.current_stream()
         for st in (self._s_maps, self._s_track, self._s_prep, self._s_map):
             st.wait_stream(cur)
@@ -570,8 +565,7 @@ class SlamPipeline:
                 if i >= 2:
                     self._s_maps.wait_event(ev_pose[i - 2])      # its map set was the "last" set of frame i-2
                 mark("maps0", i)
-                self._in_track.copy_(depths[i])
-                if not self.cam.prepare(self._in_track, rgbs[i], timestamps[i]):
+                if not self.cam.prepare(depths[i], rgbs[i], timestamps[i]):
                     raise ValueError("run_stream needs strictly increasing timestamps")
                 ev_maps[i].record()
                 mark("maps1", i)
@@ -586,8 +580,7 @@ class SlamPipeline:
                     self.cam.track_prepared()
                     mark("track1", i)
                 else:
-                    self._in_track.copy_(depths[i])
-                    self.track(self._in_track, rgbs[i], timestamps[i])
+                    self.track(depths[i], rgbs[i], timestamps[i])
                 fusion_ptr[i] = self.cam.fusion_transform_ptr()   # ring slot of frame i
                 ev_pose[i].record()
 
@@ -597,12 +590,11 @@ class SlamPipeline:
                 self._s_prep.wait_event(ev_pose[i])
                 mark("prep0", i)
                 self.points = pts
-                self._in_prep.copy_(depths[i])
                 if self.band_exchange and self.band_keys:
-                    self.sort_bands(self._in_prep, ws, fusion_ptr[i])
+                    self.sort_bands(depths[i], ws, fusion_ptr[i])
                     ev_bp[i].record()
                 else:
-                    self._backproject_with(self._in_prep, fusion_ptr[i])
+                    self._backproject_with(depths[i], fusion_ptr[i])
                     ev_bp[i].record()
                     pkg.svo_fuse_sort(ws, pts.view(-1, 3), self.depth, self.center, self.edge)
                 if i > 0:
@@ -626,8 +618,7 @@ class SlamPipeline:
             with torch.cuda.stream(self._s_map):
                 self._s_map.wait_event(ev_plan[i])
                 mark("commit0", i)
-                self._in_rgb.copy_(rgbs[i])
-                pkg.svo_fuse_commit(self._ws2[i & 1], self._in_rgb.view(-1, 3), self.depth, self.pool)
+                pkg.svo_fuse_commit(self._ws2[i & 1], rgbs[i].view(-1, 3), self.depth, self.pool)
                 ev_commit[i].record()
                 mark("commit1", i)
             if i + 1 < n:

@@ -259,6 +259,10 @@ def test_config_struct_defaults_set_get_and_environment():
         assert now["track_mode"] == 1 and now["runner_lead"] == 3 and now["march_bricks"] == before["march_bricks"]
         with pytest.raises(pkg.SvoslamError):
             pkg.configure(runner_replicas=3)
+        with pytest.raises(pkg.SvoslamError):       # retired: two map replicas, HIP-graph replay
+            pkg.configure(runner_replicas=2)
+        with pytest.raises(pkg.SvoslamError):
+            pkg.configure(graphs=1)
         with pytest.raises(pkg.SvoslamError):
             pkg.configure(track_mode=7)
         with pytest.raises(KeyError):
@@ -267,8 +271,10 @@ def test_config_struct_defaults_set_get_and_environment():
         pkg.configure(**before)
     assert pkg.get_config() == before
     code = "import sys, json; sys.path.insert(0, %r); import svoslam_pkg; print('CFG' + json.dumps(svoslam_pkg.load().get_config()))" % ROOT
-    env = dict(os.environ, **pkg.config_env(march_bricks=0, track_workers=17, runner_deferred=0))
+    env = dict(os.environ, **pkg.config_env(march_bricks=0, track_workers=17, runner_deferred=0, graphs=1, runner_replicas=2))
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-1000:]
     got = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("CFG")][0][3:])
     assert got["march_bricks"] == 0 and got["track_workers"] == 17 and got["runner_deferred"] == 0 and got["track_stream"] == 1
+    assert got["graphs"] == 0 and got["runner_replicas"] == 1          # retired values: reported and not taken
+    assert "'graphs' rejected" in r.stderr and "'runner_replicas' rejected" in r.stderr

@@ -167,8 +167,8 @@ def test_phase_api_contracts(env):
 
 
 def test_pipeline_reset_replays_identically(env):
-    """reset() (bench.py's initialisation pass relies on it): empty map + fresh tracker on the same allocations and
-    recorded graphs reproduce a fresh pipeline bit for bit"""
+    """reset() (bench.py's initialisation pass relies on it): empty map + fresh tracker on the same allocations reproduce a
+    fresh pipeline bit for bit"""
     pkg, torch, synth, pl = env
     w, h, depth, center, edge, n = 160, 120, 8, (0.0, 1.5, 0.0), 4.096, 7
     frames = [synth.render_frame(k, w, h, device="cuda") for k in range(n)]
@@ -237,10 +237,9 @@ def test_native_runner_equals_sequential(env, capacity, band):
         B.run_stream(ds[:2], cs[:2], [0, 0], views[:2])
 
 
-def test_graph_replay_and_chain_tracker_in_subprocess(env):
-    """HIP-graph replay of the launch sequences (svoslam_config.graphs = 1; off by default since round 2) together with the
-    launch-chain tracker (track_mode = 1), in a child process (settings through SVOSLAM_CONFIG): same final image, pool and pose as the default
-    (direct launches, one-launch tracker) in this process"""
+def test_chain_tracker_and_runner_settings_in_subprocess(env):
+    """the launch-chain tracker (track_mode = 1) and the scheduler's commit settings (runner_deferred, runner_lead), each in a
+    child process (settings through SVOSLAM_CONFIG): same final image, pool and pose as the default (one-launch tracker)"""
     import hashlib
     import json
     import subprocess
@@ -270,9 +269,7 @@ print("RESULT" + json.dumps([sha(P.image.cpu().numpy()), sha(P.pool.words()), sh
         assert r.returncode == 0, r.stderr[-2000:]
         return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT")][0][6:])
     base = run({})
-    assert run(dict(graphs=1, track_mode=1)) == base
-    assert run(dict(graphs=1)) == base
-    # launch chain by direct launches (work maps: iteration it applies one matrix to what iteration it - 1 stored)
+    # launch chain (work maps: iteration it applies one matrix to what iteration it - 1 stored)
     assert run(dict(track_mode=1)) == base
     # the scheduler with deferred commits (commit of frame k+1 computed beside the march of frame k, then applied: the
     # default at this image size since round 3) and with in-place commits; with and without the occupancy bricks

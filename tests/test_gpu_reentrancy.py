@@ -1,7 +1,6 @@
 """GPU tests of the library's state handling: per-stream raycast acceleration data,
-pool replacement (set_words) followed by asynchronous fusion, pool replicas (svoslam_pool_copy + svoslam_svo_fuse_commit_to,
-what the frame scheduler uses to march one replica while the next frame is committed to the other), and the runner's
-argument validation."""
+pool replacement (set_words) followed by asynchronous fusion, pool copies (svoslam_pool_copy), and the runner's argument
+validation."""
 import importlib
 import os
 
@@ -91,8 +90,9 @@ def test_set_words_then_async_fusion(env, oracle):
         B.set_words(bad)
 
 
-def test_pool_replicas_commit_to(env, oracle):
-    """svoslam_pool_copy + one plan applied to two replicas (made against either of them): both equal the plain fusion"""
+def test_pool_copy(env, oracle):
+    """svoslam_pool_copy: a byte-identical copy (size, at least the source's capacity, words) that fuses like its source --
+    source and copy both equal the plain fusion after every frame"""
     pkg, torch, synth, pl = env
     rng = np.random.default_rng(8)
     clouds = [surface_cloud(rng, 50000) for _ in range(4)]
@@ -104,56 +104,42 @@ def test_pool_replicas_commit_to(env, oracle):
     pkg.svo_from_point_cloud_async(wsr, dev[0][0], dev[0][1], depth, ref, (0, 0, 0), 1.0)
     Bp.copy_from(A)
     assert Bp.size == A.size and Bp.capacity >= A.capacity and np.array_equal(Bp.words(), A.words())
-    s2 = torch.cuda.Stream()
+    wsb = pkg.Workspace()
     for k in (1, 2, 3):
         pkg.svo_from_point_cloud_async(wsr, dev[k][0], dev[k][1], depth, ref, (0, 0, 0), 1.0)
-        planned, other = (A, Bp) if k % 2 else (Bp, A)
-        pkg.svo_fuse_sort(ws, dev[k][0], depth, (0, 0, 0), 1.0)
-        pkg.svo_fuse_plan(ws, dev[k][0].shape[0], depth, planned)
-        torch.cuda.synchronize()
-        if other.capacity < planned.capacity:      # the plan grew the replica it reserves on: the other follows
-            other.reserve(planned.capacity)
-        pkg.svo_fuse_commit_to(ws, dev[k][1], depth, other, 0, True)          # the replica the plan did not read, first
-        with torch.cuda.stream(s2):
-            pkg.svo_fuse_commit_to(ws, dev[k][1], depth, planned, 1, False)   # concurrently, own scratch slot
+        pkg.svo_from_point_cloud_async(ws, dev[k][0], dev[k][1], depth, A, (0, 0, 0), 1.0)
+        pkg.svo_from_point_cloud_async(wsb, dev[k][0], dev[k][1], depth, Bp, (0, 0, 0), 1.0)
         torch.cuda.synchronize()
         want = ref.words()
         assert A.size == Bp.size == ref.size
         assert np.array_equal(A.words(), want) and np.array_equal(Bp.words(), want), k
-    with pytest.raises(pkg.SvoslamError):          # the plan was consumed by the last application
-        pkg.svo_fuse_commit_to(ws, dev[3][1], depth, A, 0, False)
 
 
-@pytest.mark.parametrize("replicas", [2, 1])
-def test_runner_replicas_and_validation(env, replicas):
-    """the scheduler with two map replicas (opt-in) and with one (default): final image, pool, pose, counters of the sequential
-    loop; a call with bad timestamps is refused BEFORE anything is enqueued and leaves the runner usable"""
+def test_runner_and_validation(env):
+    """the scheduler: final image, pool, pose, counters of the sequential loop; a call with bad timestamps is refused BEFORE
+    anything is enqueued and leaves the runner usable"""
     pkg, torch, synth, pl = env
-    before = pkg.configure(runner_replicas=replicas)     # (taken when the runner is created)
-    try:
-        w, h, depth, center, edge, n = 160, 120, 8, (0.0, 1.5, 0.0), 4.096, 13
-        frames = [synth.render_frame(k, w, h, device="cuda") for k in range(n)]
-        views = [pl.ground_truth_view(k, synth) for k in range(n)]
-        ds, cs = [f[0] for f in frames], [f[1] for f in frames]
-        A = pl.SlamPipeline(w, h, depth, center, edge, count_steps=True)
-        for k in range(n):
-            ref = A.frame(ds[k], cs[k], k, views[k])
-        ref = ref.cpu().numpy().copy()
-        B = pl.SlamPipeline(w, h, depth, center, edge, count_steps=True, pool_capacity_nodes=1 << 12)   # grows mid-stream
-        B.run_stream(ds[:5], cs[:5], list(range(5)), views[:5])
-        with pytest.raises(pkg.SvoslamError):
-            B.run_stream(ds[5:7], cs[5:7], [4, 5], views[5:7])        # not newer than the camera's latest frame
-        with pytest.raises(pkg.SvoslamError):
-            B.run_stream(ds[5:8], cs[5:8], [5, 7, 7], views[5:8])     # not strictly increasing
-        B.run_stream(ds[5:6], cs[5:6], [5], views[5:6])               # a one-frame call
-        B.run_stream(ds[6:], cs[6:], list(range(6, n)), views[6:])
-        torch.cuda.synchronize()
-        assert np.array_equal(B.image.cpu().numpy(), ref)
-        assert A.pool.size == B.pool.size and np.array_equal(A.pool.words(), B.pool.words())
-        assert np.array_equal(A.cam.pose()[0], B.cam.pose()[0]) and np.array_equal(A.cam.pose()[1], B.cam.pose()[1])
-        assert A.counters.tolist() == B.counters.tolist()
-    finally:
-        pkg.configure(**before)
+    w, h, depth, center, edge, n = 160, 120, 8, (0.0, 1.5, 0.0), 4.096, 13
+    frames = [synth.render_frame(k, w, h, device="cuda") for k in range(n)]
+    views = [pl.ground_truth_view(k, synth) for k in range(n)]
+    ds, cs = [f[0] for f in frames], [f[1] for f in frames]
+    A = pl.SlamPipeline(w, h, depth, center, edge, count_steps=True)
+    for k in range(n):
+        ref = A.frame(ds[k], cs[k], k, views[k])
+    ref = ref.cpu().numpy().copy()
+    B = pl.SlamPipeline(w, h, depth, center, edge, count_steps=True, pool_capacity_nodes=1 << 12)   # grows mid-stream
+    B.run_stream(ds[:5], cs[:5], list(range(5)), views[:5])
+    with pytest.raises(pkg.SvoslamError):
+        B.run_stream(ds[5:7], cs[5:7], [4, 5], views[5:7])        # not newer than the camera's latest frame
+    with pytest.raises(pkg.SvoslamError):
+        B.run_stream(ds[5:8], cs[5:8], [5, 7, 7], views[5:8])     # not strictly increasing
+    B.run_stream(ds[5:6], cs[5:6], [5], views[5:6])               # a one-frame call
+    B.run_stream(ds[6:], cs[6:], list(range(6, n)), views[6:])
+    torch.cuda.synchronize()
+    assert np.array_equal(B.image.cpu().numpy(), ref)
+    assert A.pool.size == B.pool.size and np.array_equal(A.pool.words(), B.pool.words())
+    assert np.array_equal(A.cam.pose()[0], B.cam.pose()[0]) and np.array_equal(A.cam.pose()[1], B.cam.pose()[1])
+    assert A.counters.tolist() == B.counters.tolist()
 
 
 def test_obj_loader_refuses_bad_indices(env, tmp_path):
