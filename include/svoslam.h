@@ -143,10 +143,56 @@ int svoslam_pool_set_nodes(svoslam_pool *pool, const uint32_t *h_words, int32_t 
  *   paged, also when other parts of the map were fused meanwhile (resume == uninterrupted).  Refused with
  *   SVOSLAM_ERR_INVALID_ARG when the cube has been fused into while it was out.
  * svoslam_subtree_file_nodes: the file's linear tree as host words (free() them) -- a pool of its own for
- *   svoslam_pool_set_nodes.  Node indices are never re-used, so eviction does not shrink the allocation.  Blocking. */
+ *   svoslam_pool_set_nodes.  Node indices are never re-used, so eviction alone does not shrink the allocation:
+ *   svoslam_pool_compact (below) hands the memory back, and svoslam_pool_graft_subtree brings a paged-out cube back
+ *   into a pool whose nodes have been renumbered since.  Blocking.
+ * restore after a compaction: the tile indices in the file then name slots the compacted pool may have given to other
+ *   nodes, so restore also requires every slot the file names to be all-zero still (always true for a pool that was
+ *   never compacted: eviction zeroed them) and returns SVOSLAM_ERR_FORMAT, pool untouched, otherwise. */
 int svoslam_pool_evict_subtree(svoslam_pool *pool, const uint8_t *path, int32_t levels, const char *file, void *stream);
 int svoslam_pool_restore_subtree(svoslam_pool *pool, const char *file, void *stream);
 int svoslam_subtree_file_nodes(const char *file, uint32_t **h_words, int32_t *num_nodes);
+/* graft: the way back in that does not depend on node numbering.  The file is validated as by restore (magic, length,
+ *   checksum, relative child indices); its path is walked in the pool (SVOSLAM_ERR_INVALID_ARG if it leaves the tree, or
+ *   if the node has children: the cube was fused into meanwhile); the file's tiles are APPENDED at base = pool->size
+ *   (the pool grows if it has to; SVOSLAM_ERR_POOL_LIMIT beyond 2^30 nodes) with child indices base + relative index,
+ *   the node gets FLAG | base and keeps its colour word.  The file's node_index, pool_size and tile indices are not
+ *   looked at, so it works on compacted and never-compacted pools alike (on the latter the tree equals restore's, the
+ *   numbering does not).  Also SVOSLAM_ERR_INVALID_ARG when a plan of the structure chain is ahead of its commit or a
+ *   deferred commit waits for its apply: their splits take the same indices behind pool->size.  The pool grows as for
+ *   a fusion (at least doubling), so grafting into a pool that was shrunk to fit undoes the shrink.  Blocking. */
+int svoslam_pool_graft_subtree(svoslam_pool *pool, const char *file, void *stream);
+/* Compacting re-index: the pool becomes exactly the tiles reachable from the root tile (nodes 0..7) in CANONICAL ORDER --
+ * breadth-first from tile 0, each level in the order of the parent nodes' new indices, then octant 0..7: the rule evict
+ * uses below a node, applied from the root -- so two pools that hold the same tree hold the same bytes afterwards.
+ * Colour words and word0 of childless nodes are copied, word0 of a node with children becomes FLAG | 8 * (new index of
+ * its child tile); tiles nothing points to (zeroed by an eviction, or anything else) are dropped.  size becomes
+ * 8 * (reachable tiles), the device-resident size follows, pending / pending_bound become 0.
+ * Out of place: the nodes move to a fresh allocation and the old one is freed -- capacity_nodes <= 0 keeps the present
+ * capacity, otherwise the new capacity is max(capacity_nodes, size_after): this is how memory is handed back.  Peak
+ * device use is the old plus the new allocation; when capacity_nodes is smaller than size_before the new allocation
+ * is first sized for size_before (all that is known before the walk) and trimmed by one device copy, so the transient
+ * peak of that form is old + size_before + trimmed.  The march acceleration data follows the pool and is rebuilt in
+ * full by the next render; the shadow words of deferred commits (8 bytes per node of capacity, allocated by the first
+ * svo_fuse_commit_deferred) are released when the capacity shrank and allocated anew, for the new capacity, by the next
+ * deferred commit.  The next fusion or graft that does not fit grows the pool as ever (at least doubling).
+ * d_old_tile (optional, device, size_before / 8 entries): entry k = the old first-node index of the tile that became
+ * new tile k.
+ * SVOSLAM_ERR_INVALID_ARG: a plan of the structure chain is ahead of its commit, or a deferred commit waits for its
+ * apply (compacting between the two is not allowed: the same rule as for save and resize).  A plain svo_fuse_plan
+ * without its commit yet does not stop the compaction but is void afterwards -- the workspace holds node indices of the
+ * old numbering --: svo_fuse_commit* and svo_fuse_split_early then return SVOSLAM_ERR_INVALID_ARG; plan again.
+ * SVOSLAM_ERR_FORMAT: a
+ * child index that is not a multiple of 8 or lies outside size_before, or more tiles visited than size_before / 8 (a
+ * cycle or a shared tile in a foreign pool).  On any error the pool is untouched.  Blocking: waits for the whole device. */
+typedef struct {
+  int32_t size_before, size_after;         /* nodes */
+  int32_t capacity_before, capacity_after; /* nodes */
+  int32_t levels;                          /* tile levels visited, root tile = level 0 */
+  int32_t tiles_dropped;                   /* (size_before - size_after) / 8 */
+} svoslam_compact_stats;
+int svoslam_pool_compact(svoslam_pool *pool, int32_t capacity_nodes, uint32_t *d_old_tile, svoslam_compact_stats *stats,
+                         void *stream);
 /* dst becomes a byte-identical replica of src (nodes, size, at least src's capacity); dst may be zero-initialised.
  * Blocking (waits for the device). */
 int svoslam_pool_copy(svoslam_pool *dst, svoslam_pool *src, void *stream);

@@ -60,6 +60,11 @@ class FuseStats(C.Structure):
                 ("pool_size_before", C.c_int32), ("pool_size_after", C.c_int32)]
 
 
+class CompactStats(C.Structure):
+    _fields_ = [("size_before", C.c_int32), ("size_after", C.c_int32), ("capacity_before", C.c_int32), ("capacity_after", C.c_int32),
+                ("levels", C.c_int32), ("tiles_dropped", C.c_int32)]
+
+
 _lib = None
 _vp, _i32, _f32 = C.c_void_p, C.c_int32, C.c_float
 _fp = C.POINTER(C.c_float)
@@ -85,6 +90,8 @@ SIGNATURES = {
     "svoslam_pool_set_nodes": (C.c_int, [C.POINTER(_PoolStruct), C.POINTER(C.c_uint32), _i32, _vp]),
     "svoslam_pool_evict_subtree": (C.c_int, [C.POINTER(_PoolStruct), C.POINTER(C.c_uint8), _i32, C.c_char_p, _vp]),
     "svoslam_pool_restore_subtree": (C.c_int, [C.POINTER(_PoolStruct), C.c_char_p, _vp]),
+    "svoslam_pool_graft_subtree": (C.c_int, [C.POINTER(_PoolStruct), C.c_char_p, _vp]),
+    "svoslam_pool_compact": (C.c_int, [C.POINTER(_PoolStruct), _i32, _vp, C.POINTER(CompactStats), _vp]),
     "svoslam_subtree_file_nodes": (C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(_i32)]),
     "svoslam_pool_copy": (C.c_int, [C.POINTER(_PoolStruct), C.POINTER(_PoolStruct), _vp]),
     "svoslam_pool_load": (C.c_int, [C.POINTER(_PoolStruct), C.c_char_p, _fp, C.POINTER(_f32), C.POINTER(_i32), _vp]),
@@ -384,6 +391,30 @@ class Pool:
 
     def restore_subtree(self, file):
         check(lib().svoslam_pool_restore_subtree(C.byref(self._p), str(file).encode(), _stream()))
+
+    def graft_subtree(self, file):
+        """bring a paged-out sub-tree back as new tiles at the end of the pool (svoslam_pool_graft_subtree): independent of node
+        numbering, so it works after compact() where restore_subtree refuses"""
+        check(lib().svoslam_pool_graft_subtree(C.byref(self._p), str(file).encode(), _stream()))
+
+    def compact(self, capacity_nodes=0, want_map=False):
+        """re-index the pool to the tiles reachable from the root, in canonical breadth-first order (svoslam_pool_compact).
+        capacity_nodes <= 0 keeps the capacity, otherwise the new one is max(capacity_nodes, size after): 1 shrinks to fit.
+        Returns the stats as a dict; with want_map also an int32 device tensor, entry k = old first-node index of new tile k."""
+        st = CompactStats()
+        old_tile, ptr = None, None
+        if want_map:
+            import torch
+            # the call writes size_before / 8 entries, size_before being the size AFTER its own sync: take the same one here
+            # (every commit in flight reports through the pool's tracker, which the sync drains), not a host-side size that lags
+            check(lib().svoslam_pool_sync(C.byref(self._p), _stream()))
+            old_tile = torch.zeros(max(int(self._p.size) // 8, 1), dtype=torch.int32, device="cuda")
+            ptr = C.c_void_p(old_tile.data_ptr())
+        check(lib().svoslam_pool_compact(C.byref(self._p), int(capacity_nodes), ptr, C.byref(st), _stream()))
+        stats = {n: int(getattr(st, n)) for n, _ in CompactStats._fields_}
+        if want_map:
+            return stats, old_tile[:stats["size_after"] // 8]
+        return stats
 
     def copy_from(self, other):
         """become a byte-identical replica of `other` (blocking)"""

@@ -153,6 +153,15 @@ int svoslam_pool_restore_subtree(svoslam_pool *pool, const char *file, void *str
   NEED_DEVICE();
   return pool_restore_subtree(pool, file, S(stream));
 }
+int svoslam_pool_graft_subtree(svoslam_pool *pool, const char *file, void *stream) {
+  NEED_DEVICE();
+  return pool_graft_subtree(pool, file, S(stream));
+}
+int svoslam_pool_compact(svoslam_pool *pool, int32_t capacity_nodes, uint32_t *d_old_tile, svoslam_compact_stats *stats,
+                         void *stream) {
+  NEED_DEVICE();
+  return pool_compact(pool, capacity_nodes, d_old_tile, stats, S(stream));
+}
 int svoslam_subtree_file_nodes(const char *file, uint32_t **h_words, int32_t *num_nodes) { return subtree_file_nodes(file, h_words, num_nodes); }
 int svoslam_pool_copy(svoslam_pool *dst, svoslam_pool *src, void *stream) {
   NEED_DEVICE();

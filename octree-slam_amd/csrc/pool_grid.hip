@@ -154,6 +154,18 @@ bool pool_shadow_pending(svoslam_pool *pool) {
   return it != g_accel.end() && it->second->deferred_pending;
 }
 
+// after the pool moved to a SMALLER allocation (pool_adopt_storage; the device is idle, no deferred commit is pending): the
+// shadow words go back with it, and the next deferred commit allocates them for the new capacity
+void pool_accel_trim_shadow(svoslam_pool *pool) {
+  if (!pool || !pool->d_data) return;
+  std::lock_guard<std::mutex> lock(g_mu);
+  auto it = g_accel.find(pool->d_data);
+  if (it == g_accel.end() || it->second->deferred_pending || it->second->shadow_nodes <= (size_t)pool->capacity) return;
+  it->second->shadow.release();
+  it->second->shadow_nodes = 0;
+  it->second->epoch = 0;
+}
+
 std::shared_ptr<PoolAccel> pool_accel_find(const uint32_t *d_data) {
   if (!d_data) return nullptr;
   std::lock_guard<std::mutex> lock(g_mu);

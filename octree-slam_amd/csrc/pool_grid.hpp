@@ -106,6 +106,7 @@ int pool_shadow_begin(svoslam_pool *pool, hipStream_t stream, unsigned long long
 int pool_shadow_current(svoslam_pool *pool, unsigned long long **d_shadow, uint32_t *epoch);  // of the pending deferred commit
 void pool_shadow_end(svoslam_pool *pool);
 bool pool_shadow_pending(svoslam_pool *pool);
+void pool_accel_trim_shadow(svoslam_pool *pool);  // releases shadow words sized for more than pool->capacity (after a shrinking compaction)
 
 // enqueue on `stream`: bring the grid of `pa` up to date with its pool (full build or dirty blocks only); returns the grid
 // want_bricks: also bring the occupancy bricks up to date (allocating them on first use); *d_bricks = the field, or

@@ -16,9 +16,18 @@
 //            cube meanwhile (then the node has children again and restore refuses).  Fusions elsewhere append their
 //            tiles behind the evicted ones exactly as they would have without the eviction.
 //
-// Indices are never re-used (node numbering has to stay that of the uninterrupted run), so eviction does not shrink the
-// allocation: what it buys is the host copy plus a device range that is no longer touched; a compacting re-index is a
-// different operation (it changes every node index).  Both calls are blocking and wait for the whole device.
+// Indices are never re-used (node numbering has to stay that of the uninterrupted run), so eviction alone does not shrink
+// the allocation: what it buys is the host copy plus a device range that is no longer touched.  The compacting re-index
+// that hands the memory back is svoslam_pool_compact (pool_compact.hip); it changes every node index, so afterwards
+//
+//   graft    is the way back in: the file's stand-alone tree is APPENDED at the end of the pool (child indices = base +
+//            relative index) and the node at the file's path is pointed at it -- no use of the tile indices the file
+//            recorded, so it works on compacted and never-compacted pools alike;
+//   restore  refuses (SVOSLAM_ERR_FORMAT) unless every tile slot the file names is still all-zero in the pool: after evict ->
+//            compact -> more fusion its other two checks can pass while the slots belong to live nodes.  On a pool that was
+//            never compacted the slots are zero (eviction zeroed them, indices are never re-used); a live tile other than the
+//            root tile is never all-zero (child tiles are born with alpha 127).
+// All calls are blocking and wait for the whole device.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -77,6 +86,15 @@ __global__ __launch_bounds__(256) void page_scatter_kernel(u32 *__restrict__ poo
   uint2 nd = blob[i];
   if (nd.x & kFlag) nd.x = kFlag | (tiles[(nd.x & kMask) >> 3] & kMask);
   reinterpret_cast<uint2 *>(pool)[tiles[i >> 3] + (i & 7u)] = nd;
+}
+
+// restore's guard: OR of every word of the tile slots the file names (8 lanes per tile, one node each)
+__global__ __launch_bounds__(256) void page_slots_used_kernel(const u32 *__restrict__ pool, const u32 *__restrict__ tiles, u32 n,
+                                                              u32 *__restrict__ used) {
+  const u32 i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n * 8u) return;
+  const uint2 nd = reinterpret_cast<const uint2 *>(pool)[tiles[i >> 3] + (i & 7u)];
+  if (nd.x | nd.y) atomicOr(used, 1u);
 }
 
 struct SubtreeHeader {
@@ -211,17 +229,31 @@ int pool_evict_subtree(svoslam_pool *pool, const uint8_t *path, int levels, cons
   return SVOSLAM_OK;
 }
 
-int pool_restore_subtree(svoslam_pool *pool, const char *file, hipStream_t stream) {
-  if (!pool || !pool->d_data || !file) return SVOSLAM_ERR_INVALID_ARG;
+// What restore and graft accept of a file, checked alike: magic, version, levels, a length that holds num_tiles tiles, the
+// checksum, and relative child indices that stay inside the file's own tree.  What the file says about the pool it left
+// (node_index, pool_size, the tile indices) is restore's business alone.
+static int read_subtree_file(const char *file, SubtreeHeader *h, std::vector<u32> *tiles, std::vector<u32> *nodes) {
   FILE *f = fopen(file, "rb");
   if (!f) return SVOSLAM_ERR_IO;
-  SubtreeHeader h;
-  if (fread(&h, sizeof(h), 1, f) != 1 || memcmp(h.magic, "SVOSUBT1", 8) != 0 || h.version != 1 || h.levels < 1 ||
-      h.levels > SVOSLAM_MAX_DEPTH || !tiles_fit_file(f, h.num_tiles)) { fclose(f); return SVOSLAM_ERR_FORMAT; }
-  std::vector<u32> tiles(h.num_tiles), nodes((size_t)h.num_tiles * 16);
-  const bool ok = fread(tiles.data(), 4, tiles.size(), f) == tiles.size() && fread(nodes.data(), 4, nodes.size(), f) == nodes.size();
+  if (fread(h, sizeof(*h), 1, f) != 1 || memcmp(h->magic, "SVOSUBT1", 8) != 0 || h->version != 1 || h->levels < 1 ||
+      h->levels > SVOSLAM_MAX_DEPTH || !tiles_fit_file(f, h->num_tiles)) { fclose(f); return SVOSLAM_ERR_FORMAT; }
+  tiles->resize(h->num_tiles);
+  nodes->resize((size_t)h->num_tiles * 16);
+  const bool ok = fread(tiles->data(), 4, tiles->size(), f) == tiles->size() && fread(nodes->data(), 4, nodes->size(), f) == nodes->size();
   fclose(f);
-  if (!ok || fnv1a(nodes.data(), nodes.size() * 4, fnv1a(tiles.data(), tiles.size() * 4)) != h.checksum) return SVOSLAM_ERR_FORMAT;
+  if (!ok || fnv1a(nodes->data(), nodes->size() * 4, fnv1a(tiles->data(), tiles->size() * 4)) != h->checksum) return SVOSLAM_ERR_FORMAT;
+  for (size_t i = 0; i < (size_t)h->num_tiles * 8; i++) {
+    const u32 w0 = (*nodes)[2 * i];
+    if ((w0 & kFlag) && ((w0 & kMask) & 7u || ((w0 & kMask) >> 3) >= h->num_tiles)) return SVOSLAM_ERR_FORMAT;
+  }
+  return SVOSLAM_OK;
+}
+
+int pool_restore_subtree(svoslam_pool *pool, const char *file, hipStream_t stream) {
+  if (!pool || !pool->d_data || !file) return SVOSLAM_ERR_INVALID_ARG;
+  SubtreeHeader h;
+  std::vector<u32> tiles, nodes;
+  SVO_TRY(read_subtree_file(file, &h, &tiles, &nodes));
   SVO_HIP(hipDeviceSynchronize());
   SVO_TRY(pool_sync(pool, stream));
   if (pool->size < h.pool_size) return SVOSLAM_ERR_FORMAT;  // not the pool (or not the state) the sub-tree came from
@@ -232,19 +264,26 @@ int pool_restore_subtree(svoslam_pool *pool, const char *file, hipStream_t strea
     std::sort(sorted.begin(), sorted.end());
     if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return SVOSLAM_ERR_FORMAT;
   }
-  for (size_t i = 0; i < (size_t)h.num_tiles * 8; i++) {
-    const u32 w0 = nodes[2 * i];
-    if ((w0 & kFlag) && ((w0 & kMask) & 7u || ((w0 & kMask) >> 3) >= h.num_tiles)) return SVOSLAM_ERR_FORMAT;
-  }
   u32 node = 0, w0 = 0;
   SVO_TRY(walk_path(pool, h.path, h.levels, &node, &w0));
   if (node != h.node_index) return SVOSLAM_ERR_FORMAT;
   if (w0 & kFlag) return SVOSLAM_ERR_INVALID_ARG;  // the cube was fused into while it was paged out
   DeviceBuffer d_tiles, d_nodes;
-  SVO_TRY(d_tiles.reserve(tiles.size() * 4));
+  SVO_TRY(d_tiles.reserve(tiles.size() * 4 + 4));  // (+ the guard's answer behind the indices)
   int rc = d_nodes.reserve(nodes.size() * 4);
   if (rc != SVOSLAM_OK) { d_tiles.release(); return rc; }
   hipError_t e = hipMemcpy(d_tiles.ptr, tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {  // every slot the file names must still be empty: a compaction since the eviction re-used them
+    u32 used = 0;
+    u32 *d_used = d_tiles.as<u32>() + tiles.size();
+    e = hipMemcpy(d_used, &used, 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+      page_slots_used_kernel<<<cdiv((long long)h.num_tiles * 8, 256), 256, 0, stream>>>(pool->d_data, d_tiles.as<u32>(), h.num_tiles, d_used);
+      e = hipMemcpyAsync(&used, d_used, 4, hipMemcpyDeviceToHost, stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    }
+    if (e == hipSuccess && used) { d_tiles.release(); d_nodes.release(); return SVOSLAM_ERR_FORMAT; }
+  }
   if (e == hipSuccess) e = hipMemcpy(d_nodes.ptr, nodes.data(), nodes.size() * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     page_scatter_kernel<<<cdiv((long long)h.num_tiles * 8, 256), 256, 0, stream>>>(pool->d_data, d_tiles.as<u32>(), h.num_tiles, d_nodes.as<uint2>());
@@ -256,6 +295,34 @@ int pool_restore_subtree(svoslam_pool *pool, const char *file, hipStream_t strea
   pool_accel_invalidate(pool);
   if (e != hipSuccess) { set_last_error("pool_restore_subtree", e); return SVOSLAM_ERR_HIP; }
   return SVOSLAM_OK;
+}
+
+// The sub-tree comes back as NEW tiles behind pool->size: nothing of the numbering the file recorded (node_index, pool_size,
+// tile indices) is looked at, only its stand-alone tree and its octant path.
+int pool_graft_subtree(svoslam_pool *pool, const char *file, hipStream_t stream) {
+  if (!pool || !pool->d_data || !file) return SVOSLAM_ERR_INVALID_ARG;
+  SubtreeHeader h;
+  std::vector<u32> tiles, nodes;
+  SVO_TRY(read_subtree_file(file, &h, &tiles, &nodes));
+  SVO_HIP(hipDeviceSynchronize());
+  SVO_TRY(pool_sync(pool, stream));
+  if (pool_planned_ahead(pool) > 0 || pool_shadow_pending(pool)) return SVOSLAM_ERR_INVALID_ARG;  // their splits allocate behind pool->size too
+  u32 node = 0, w0 = 0;
+  {
+    const int rc = walk_path(pool, h.path, h.levels, &node, &w0);
+    if (rc != SVOSLAM_OK) return rc == SVOSLAM_ERR_HIP ? rc : SVOSLAM_ERR_INVALID_ARG;  // the path leaves the tree
+  }
+  if (w0 & kFlag) return SVOSLAM_ERR_INVALID_ARG;  // the cube was fused into while it was paged out
+  const int64_t base = pool->size, need = base + 8ll * h.num_tiles;
+  if (need > (int64_t)kMask + 1) return SVOSLAM_ERR_POOL_LIMIT;
+  SVO_TRY(pool_reserve(pool, (int32_t)need, stream));
+  for (size_t i = 0; i < (size_t)h.num_tiles * 8; i++)
+    if (nodes[2 * i] & kFlag) nodes[2 * i] = kFlag | (((u32)base + (nodes[2 * i] & kMask)) & kMask);
+  SVO_HIP(hipMemcpy(pool->d_data + 2 * (size_t)base, nodes.data(), nodes.size() * 4, hipMemcpyHostToDevice));
+  const u32 flagged = kFlag | ((u32)base & kMask);
+  SVO_HIP(hipMemcpy(pool->d_data + 2 * (size_t)node, &flagged, 4, hipMemcpyHostToDevice));
+  pool_accel_invalidate(pool);
+  return pool_set_size(pool, (int32_t)need, stream);
 }
 
 // the stand-alone linear tree of a paged-out sub-tree (its 8 top nodes first): host words for svoslam_pool_set_nodes

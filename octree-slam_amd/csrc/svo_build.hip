@@ -1136,6 +1136,7 @@ struct PoolTracker {
   InFlight q[kSlots];  // oldest first
   int count = 0, next = 0;
   int planned_ahead = 0;  // svo_fuse_plan_structure calls whose commit has not been enqueued yet (their reservations must survive pool_sync)
+  uint32_t numbering = 0;  // bumped when every node index changes (pool_adopt_storage): a plan holds indices of the numbering it read
 };
 
 static PoolTracker *tracker_of(svoslam_pool *pool) { return reinterpret_cast<PoolTracker *>(pool->tracker); }
@@ -1342,6 +1343,38 @@ int pool_reset(svoslam_pool *pool, hipStream_t stream) {
 int pool_reserve(svoslam_pool *pool, int32_t capacity_nodes, hipStream_t stream) {
   if (!pool) return SVOSLAM_ERR_INVALID_ARG;
   return grow_pool(pool, capacity_nodes, stream);
+}
+
+// ---- what pool_compact.hip needs of the bookkeeping above ----------------------------------------
+// plans of the structure chain whose commit has not been enqueued yet (they hold node indices of the present numbering)
+int pool_planned_ahead(svoslam_pool *pool) { return tracker_of(pool) ? tracker_of(pool)->planned_ahead : 0; }
+
+// The pool's nodes now live in `fresh` (size_nodes of them, room for capacity_nodes): the march acceleration data follows
+// the pointer as in grow_pool and is invalidated for a full rebuild, the old allocation is freed, host and device size
+// and the reservations are reset as in pool_set_nodes.  The caller has synchronised the device and the pool.
+int pool_adopt_storage(svoslam_pool *pool, uint32_t *fresh, int32_t size_nodes, int32_t capacity_nodes, hipStream_t stream) {
+  SVO_TRY(ensure_device_size(pool, stream));
+  tracker_of(pool)->numbering++;  // a svo_fuse_plan without its commit yet is void from here on (commit_impl refuses it)
+  pool_accel_rebind(pool->d_data, fresh);
+  u32 *old = pool->d_data;
+  pool->d_data = fresh;
+  pool->capacity = capacity_nodes;
+  pool->size = size_nodes;
+  pool->pending = 0; pool->pending_bound = 0;
+  pool_accel_invalidate(pool, 0, false);  // the same words under new indices
+  pool_accel_trim_shadow(pool);           // a deferred-commit shadow sized for a larger capacity goes back too
+  if (old) SVO_HIP(hipFree(old));
+  SVO_HIP(hipMemcpy(pool->d_size, &pool->size, 4, hipMemcpyHostToDevice));
+  return SVOSLAM_OK;
+}
+
+// size bookkeeping after nodes were appended behind pool->size by something other than a fusion (pool_paging.hip: graft)
+int pool_set_size(svoslam_pool *pool, int32_t size_nodes, hipStream_t stream) {
+  SVO_TRY(ensure_device_size(pool, stream));
+  pool->size = size_nodes;
+  pool->pending = 0; pool->pending_bound = 0;
+  SVO_HIP(hipMemcpy(pool->d_size, &pool->size, 4, hipMemcpyHostToDevice));
+  return SVOSLAM_OK;
 }
 
 // ---- checkpoint / resume -------------------------------------------------------------
@@ -1773,6 +1806,12 @@ int pool_structure_begin(svoslam_pool *pool, hipStream_t stream) {
   return SVOSLAM_OK;
 }
 
+// svoslam_pool_compact re-indexed the pool after this workspace's plan read it: the node indices the plan left in the workspace
+// (leaf_f, leaf_start, rec_front) mean other nodes now, or none (a shrunk allocation)
+static bool plan_renumbered(const svoslam_workspace *ws, svoslam_pool *pool) {
+  return ws->planned_pool == pool && tracker_of(pool) && tracker_of(pool)->numbering != ws->planned_numbering;
+}
+
 static int fuse_plan_impl(svoslam_workspace *ws, int n, int depth, svoslam_pool *pool, bool structure, hipStream_t stream) {
   if (!ws || !pool || n < 0) return SVOSLAM_ERR_INVALID_ARG;
   if (depth < 1 || depth > SVOSLAM_MAX_DEPTH) return SVOSLAM_ERR_DEPTH;
@@ -1829,6 +1868,7 @@ static int fuse_plan_impl(svoslam_workspace *ws, int n, int depth, svoslam_pool 
   }
   ws->planned_n = n;
   ws->planned_pool = pool;
+  ws->planned_numbering = tracker_of(pool)->numbering;
   if (structure) { ws->early_split_pool = pool; tracker_of(pool)->planned_ahead++; ws->structure_planned = true; }  // the commit: leaf kernel (links again, same values; marks) + straddlers
   pool->pending_bound += 8 * rmax;  // reserved from now on
   return SVOSLAM_OK;
@@ -1852,6 +1892,7 @@ int svo_fuse_split_early(svoslam_workspace *ws, int n, int depth, svoslam_pool *
   if (ws->planned_n != n || ws->planned_pool != pool || pool_shadow_pending(pool)) return SVOSLAM_ERR_INVALID_ARG;
   ws->early_split_pool = nullptr;
   if (n == 0) return SVOSLAM_OK;
+  if (plan_renumbered(ws, pool)) return SVOSLAM_ERR_INVALID_ARG;
   int split_blocks = (int)cdiv(max_records(n, depth), 256);
   if (split_blocks > 2048) split_blocks = 2048;
   {
@@ -1875,6 +1916,10 @@ static int commit_impl(svoslam_workspace *ws, const uint8_t *d_colors, int n, in
   if (pool_shadow_pending(pool)) return SVOSLAM_ERR_INVALID_ARG;  // a deferred commit of this pool has not been applied
   if (depth < 1 || depth > SVOSLAM_MAX_DEPTH) return SVOSLAM_ERR_DEPTH;
   if (ws->planned_n != n) return SVOSLAM_ERR_INVALID_ARG;  // svo_fuse_plan has not run for this batch
+  if (n > 0 && plan_renumbered(ws, pool)) {  // the plan is void: its leaf and split indices are those of the old numbering
+    ws->planned_n = -1;
+    return SVOSLAM_ERR_INVALID_ARG;
+  }
   ws->planned_n = -1;
   ws->deferred_pool = nullptr;
   const bool early = ws->early_split_pool != nullptr;

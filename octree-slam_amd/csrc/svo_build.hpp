@@ -17,6 +17,12 @@ int pool_copy(svoslam_pool *dst, svoslam_pool *src, hipStream_t stream);
 int pool_evict_subtree(svoslam_pool *pool, const uint8_t *path, int levels, const char *file, hipStream_t stream);
 int pool_restore_subtree(svoslam_pool *pool, const char *file, hipStream_t stream);
 int subtree_file_nodes(const char *file, uint32_t **h_words, int32_t *num_nodes);
+// re-indexing (pool_compact.hip) and the bookkeeping it shares with svo_build.hip
+int pool_compact(svoslam_pool *pool, int32_t capacity_nodes, uint32_t *d_old_tile, svoslam_compact_stats *stats, hipStream_t stream);
+int pool_graft_subtree(svoslam_pool *pool, const char *file, hipStream_t stream);
+int pool_planned_ahead(svoslam_pool *pool);
+int pool_adopt_storage(svoslam_pool *pool, uint32_t *fresh, int32_t size_nodes, int32_t capacity_nodes, hipStream_t stream);
+int pool_set_size(svoslam_pool *pool, int32_t size_nodes, hipStream_t stream);
 int pool_load(svoslam_pool *pool, const char *path, float center[3], float *edge, int *depth, hipStream_t stream);
 int svo_from_point_cloud_async(svoslam_workspace *ws, const float *d_points, const uint8_t *d_colors, int n, int depth,
                                svoslam_pool *pool, const float center[3], float edge, hipStream_t stream);

@@ -66,6 +66,7 @@ struct svoslam_workspace {
   bool structure_planned = false;                          // ... by svo_fuse_plan_structure (its reservation is released by its commit)
   long long keyrange_bound = 0;                            // key-range commit: the plan's reservation, released by svo_fuse_keyrange_apply's size readback
   const void *planned_pool = nullptr;                      // the pool svo_fuse_plan read (its reservation is already booked)
+  unsigned int planned_numbering = 0;                      // ... and its node numbering then (svoslam_pool_compact starts a new one)
   // `small` (4 KB of totals / bases / counters) is zeroed when it is created: the planner's any_valid word and arrival
   // ticket must start at zero (every plan leaves them at zero).  Blocking, once per workspace.
   int reserve_small() {
