@@ -840,7 +840,11 @@ __global__ __launch_bounds__(THREADS, SVO_AHEAD_WAVES) void cone_trace_brick_ker
       // children (gq.x = flag | tile >= 2^30) ends the walk of LOD 8 only
       // (round 6: a sample whose LOD is coarser than the grid level has asked the PYRAMID for the cell of its own level lv = LOD: the
       // same rule one level up -- a childless node at gq.x <= lv ends the walk, a level-lv node with children ends the walk of LOD lv)
-      const uint32_t lv = lod_ < GRID ? (uint32_t)lod_ : (uint32_t)GRID;
+      // An LOD <= 0 walks no level at all: the reference reads NODE 0's word (:107 with node_idx = 0), which neither entry holds.  Such
+      // a sample has asked the level grid (it is not `coarse`), so lv = GRID for it as for every LOD >= GRID: the unsigned compare below
+      // fails against a node with children (lod_ - GRID wraps) as it does against a childless one (lod_ - gq.x wraps), and the sample takes
+      // the rare path, where walk_sample reads octree[1].  (The same test as `coarse`: one select on a mask the step has anyway.)
+      const uint32_t lv = (uint32_t)(lod_ - 1) < (uint32_t)(GRID - 1) ? (uint32_t)lod_ : (uint32_t)GRID;
       const uint32_t depth_g = gq.x < kFlag ? gq.x : lv;
       const uint32_t top_g = gq.x < kFlag ? 127u : lv;   // the LODs it answers: depth_g .. top_g
       const bool by_grid = (uint32_t)lod_ - depth_g <= top_g - depth_g;
@@ -921,7 +925,7 @@ __global__ __launch_bounds__(THREADS, SVO_AHEAD_WAVES) void cone_trace_brick_ker
       }
       int depth;
       const bool decided = decode(e, gq, lod, oct12, depth, retired);
-      float new_dist = ldexpf(P.size, -depth);  // (decided: depth in 1..12)
+      float new_dist = ldexpf(P.size, -depth);  // (decided: depth in 1 .. BL -- an LOD <= 0 is never decided, see decode)
       bool full_form = false;
       int depth_raw = depth;   // (the level as the reference counts it, before the clip at 0: what the bursts predict with)
 #ifdef SVO_BRICK_DIAG
@@ -1491,7 +1495,7 @@ int cone_trace_svo(uint8_t *d_pos, int width, int height, int row_first, int row
     auto launch = [&](auto kernel) {
       kernel<<<grid, kTraceThreads, (size_t)brick_march_lds_pad(), stream>>>(out, d_octree, d_grid, d_bricks, d_table, alpha_lut, P, d_steps, slots);
     };
-    // svoslam_config.march_ahead: < 0 = cone_trace_brick_kernel; n >= 0 = the march one sample ahead from step n + 1 on
+    // svoslam_config.march_ahead: < 0 = one sample per iteration throughout (B = 0); n >= 0 = bursts of kAheadBurst samples from step n + 1 on
     const int ahead = config().march_ahead;
     P.spec_from = ahead;
     if (ahead >= 0) {

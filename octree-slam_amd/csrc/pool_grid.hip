@@ -214,8 +214,33 @@ __device__ inline uint2 grid_entry(const uint2 *__restrict__ nodes, uint32_t xi,
   return out;
 }
 
+// Node 0's colour word (pool_grid.hpp "NODE 0"), by every workgroup of the grid's update (part of parts, any number of lanes each):
+// node0[par] = the word as this refresh sees it, node0[par ^ 1] = as the previous one saw it (which nothing writes during this launch).
+// Level-1 cell 0 of the pyramid always; where node 0 is childless and its word is not the one octant 0's entries were written with,
+// all of them: the cells of octant 0 at every level 1 .. G, each (1, word).
+__device__ inline void pool_grid_node0(const uint2 *__restrict__ nodes, uint2 *__restrict__ grid, uint32_t *node0, int par, uint32_t part,
+                                       uint32_t parts) {
+  constexpr int G = kPoolGridLevel;
+  const uint2 n0 = nodes[0];
+  if (part == 0 && threadIdx.x == 0) {
+    grid[((size_t)1 << (3 * G)) + pyr_offset(1)] = grid_entry_level(nodes, 0u, 0u, 0u, 1);
+    node0[par] = n0.y;
+  }
+  if ((n0.x & kFlag) || node0[par ^ 1] == n0.y) return;
+  const uint2 entry = make_uint2(1u, n0.y);
+  for (int l = 1; l <= G; l++) {   // octant 0 at level l: (2^(l-1))^3 cells
+    const int hb = l - 1;
+    uint2 *at = l < G ? grid + ((size_t)1 << (3 * G)) + pyr_offset_rt(l) : grid;
+    for (uint32_t c = part * blockDim.x + threadIdx.x; c < (1u << (3 * hb)); c += parts * blockDim.x) {
+      const uint32_t m = (1u << hb) - 1u, xi = c & m, yi = (c >> hb) & m, zi = c >> (2 * hb);
+      at[(zi << (2 * l)) | (yi << l) | xi] = entry;
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void pool_grid_build_kernel(const uint32_t *__restrict__ octree, uint2 *__restrict__ grid,
-                                                              uint32_t *__restrict__ dirty_a, uint32_t *__restrict__ dirty_b) {
+                                                              uint32_t *__restrict__ dirty_a, uint32_t *__restrict__ dirty_b,
+                                                              uint32_t *__restrict__ node0, int node0_par) {
   constexpr int G = kPoolGridLevel;
   constexpr uint32_t kAxisMask = (1u << G) - 1u;
   const uint32_t e = blockIdx.x * 256u + threadIdx.x;
@@ -224,6 +249,7 @@ __global__ __launch_bounds__(256) void pool_grid_build_kernel(const uint32_t *__
   // every mark made so far is served by this build (not those of a deferred commit still running: dirty_b == nullptr)
   if (e < (uint32_t)kPoolGridDirtyWords) { dirty_a[e] = 0u; if (dirty_b) dirty_b[e] = 0u; }
   if (e == 0) { dirty_a[kPoolGridCountOffset] = 0u; if (dirty_b) dirty_b[kPoolGridCountOffset] = 0u; }
+  if (e == 0) node0[node0_par] = octree[1];   // (every entry is new: nothing to compare)
 }
 
 // ---- occupancy bricks (pool_grid.hpp) ----------------------------------------------------------------------------------
@@ -581,8 +607,10 @@ __device__ inline void pool_grid_update_blocks(const uint2 *__restrict__ nodes, 
 }
 
 __global__ __launch_bounds__(kUpdateThreads) void pool_grid_update_kernel(const uint32_t *__restrict__ octree, uint2 *__restrict__ grid,
-                                                                          uint32_t *__restrict__ dirty_a, uint32_t *__restrict__ dirty_b) {
+                                                                          uint32_t *__restrict__ dirty_a, uint32_t *__restrict__ dirty_b,
+                                                                          uint32_t *node0, int node0_par) {
   pool_grid_update_blocks(reinterpret_cast<const uint2 *>(octree), grid, dirty_a, dirty_b, blockIdx.x, kUpdateBlocks);
+  pool_grid_node0(reinterpret_cast<const uint2 *>(octree), grid, node0, node0_par, blockIdx.x, kUpdateBlocks);
 }
 
 // The refresh before a march in ONE launch (round 3): workgroups [0, kRefreshBrickBlocks) rebuild the listed bricks, the rest
@@ -599,7 +627,8 @@ template <int C, int S>
 __global__ __launch_bounds__(kBrickThreads) void pool_refresh_kernel(const uint32_t *__restrict__ octree, uint2 *grid, uint16_t *__restrict__ bricks,
                                                                       uint32_t *__restrict__ touched, uint32_t *dirty_a, uint32_t *dirty_b,
                                                                       int trust_mip, int par_a, int par_b, unsigned brick_blocks,
-                                                                      uint32_t *__restrict__ tile_cost, uint32_t *__restrict__ tile_order, int n_tiles) {
+                                                                      uint32_t *__restrict__ tile_cost, uint32_t *__restrict__ tile_order, int n_tiles,
+                                                                      uint32_t *node0, int node0_par) {
   if (n_tiles > 0 && blockIdx.x == gridDim.x - 1) { tile_order_block(tile_cost, tile_order, n_tiles); return; }  // (the march's tile order: pool_grid.hpp)
   const uint2 *nodes = reinterpret_cast<const uint2 *>(octree);
   // (the bricks' workgroups first: they are the long ones; 2048 nearly empty grid workgroups ahead of them cost the launch 20 us)
@@ -608,6 +637,7 @@ __global__ __launch_bounds__(kBrickThreads) void pool_refresh_kernel(const uint3
   const unsigned bb = blockIdx.x;
   if (bb >= brick_blocks) {
     pool_grid_update_blocks(nodes, grid, dirty_a, dirty_b, bb - brick_blocks, kRefreshGridBlocks);
+    pool_grid_node0(nodes, grid, node0, node0_par, bb - brick_blocks, kRefreshGridBlocks);
     // ... and the childless siblings of the listed bricks whose commit created them (brick_siblings_listed)
     const BrickRings rs = brick_rings(dirty_a, dirty_b, par_a, par_b, bb == brick_blocks && threadIdx.x == 0, kSibCountOffset);
     if (!brick_rings_lost(dirty_a, dirty_b, par_a, par_b))  // (a lapped ring zeroes every group: nothing to complete)
@@ -697,6 +727,9 @@ int pool_accel_refresh(PoolAccel *pa, const uint32_t *d_octree, hipStream_t stre
   }
   for (int k = 0; k < 2; k++) serve[k] = serve_idx[k] >= 0 ? pa->d_dirty[serve_idx[k]] : nullptr;
   uint2 *grid = pa->grid.as<uint2>();
+  // node 0's word, which no mark covers (pool_grid.hpp "NODE 0"): this refresh writes word [par], reads the previous one's
+  uint32_t *node0 = pa->d_dirty[0] + kPoolGridNode0Offset;
+  const int node0_par = (int)(pa->node0_served++ & 1u);
   const bool use_bricks = pa->bricks && shift >= 0;
   // once a pool has bricks every refresh keeps them current, whatever the mode of the render that asks
   const bool bricks_all = use_bricks && (fresh || !pa->bricks_valid);
@@ -705,8 +738,8 @@ int pool_accel_refresh(PoolAccel *pa, const uint32_t *d_octree, hipStream_t stre
   if (use_bricks) {
     const int trust = pa->mip_consistent ? 1 : 0;  // (PoolAccel::mip_consistent: rebuild 65 -> 39 us at cfg3)
     if (bricks_all) {
-      if (fresh) pool_grid_build_kernel<<<(unsigned)(kCells / 256), 256, 0, stream>>>(d_octree, grid, serve[0], serve[1]);
-      else pool_grid_update_kernel<<<kUpdateBlocks, kUpdateThreads, 0, stream>>>(d_octree, grid, serve[0], serve[1]);
+      if (fresh) pool_grid_build_kernel<<<(unsigned)(kCells / 256), 256, 0, stream>>>(d_octree, grid, serve[0], serve[1], node0, node0_par);
+      else pool_grid_update_kernel<<<kUpdateBlocks, kUpdateThreads, 0, stream>>>(d_octree, grid, serve[0], serve[1], node0, node0_par);
       brick_clear_kernel<<<2048, 256, 0, stream>>>(pa->bricks, pa->d_brick_touched);
       if (shift == 0) brick_rebuild_kernel<0><<<kBrickBlocks, kBrickThreads, 0, stream>>>(d_octree, grid, pa->bricks, pa->d_brick_touched, serve[0], serve[1], trust, par_a, par_b);
       else brick_rebuild_kernel<1><<<kBrickBlocks, kBrickThreads, 0, stream>>>(d_octree, grid, pa->bricks, pa->d_brick_touched, serve[0], serve[1], trust, par_a, par_b);
@@ -715,8 +748,8 @@ int pool_accel_refresh(PoolAccel *pa, const uint32_t *d_octree, hipStream_t stre
       // the march -- rays reach the surfaces before the rebuild does and pay tree walks: march 0.325 -> 0.395 ms; two launches;
       // 4096 workgroups x 2 bricks per wavefront -- kernel 55 -> 40 us, frame rate lower: DESIGN.md section 4.)
       const int extra = tile_cost && tile_order && n_tiles > 0 ? 1 : 0;  // one more workgroup: the tile order of the caller's march
-      if (shift == 0) pool_refresh_kernel<kRefreshChains, 0><<<kRefreshBrickBlocks + kRefreshGridBlocks + extra, kBrickThreads, 0, stream>>>(d_octree, grid, pa->bricks, pa->d_brick_touched, serve[0], serve[1], trust, par_a, par_b, kRefreshBrickBlocks, tile_cost, tile_order, extra ? n_tiles : 0);
-      else pool_refresh_kernel<kRefreshChains, 1><<<kRefreshBrickBlocks + kRefreshGridBlocks + extra, kBrickThreads, 0, stream>>>(d_octree, grid, pa->bricks, pa->d_brick_touched, serve[0], serve[1], trust, par_a, par_b, kRefreshBrickBlocks, tile_cost, tile_order, extra ? n_tiles : 0);
+      if (shift == 0) pool_refresh_kernel<kRefreshChains, 0><<<kRefreshBrickBlocks + kRefreshGridBlocks + extra, kBrickThreads, 0, stream>>>(d_octree, grid, pa->bricks, pa->d_brick_touched, serve[0], serve[1], trust, par_a, par_b, kRefreshBrickBlocks, tile_cost, tile_order, extra ? n_tiles : 0, node0, node0_par);
+      else pool_refresh_kernel<kRefreshChains, 1><<<kRefreshBrickBlocks + kRefreshGridBlocks + extra, kBrickThreads, 0, stream>>>(d_octree, grid, pa->bricks, pa->d_brick_touched, serve[0], serve[1], trust, par_a, par_b, kRefreshBrickBlocks, tile_cost, tile_order, extra ? n_tiles : 0, node0, node0_par);
       if (extra && order_done) *order_done = true;
     }
     for (int k = 0; k < 2; k++)
@@ -737,8 +770,8 @@ int pool_accel_refresh(PoolAccel *pa, const uint32_t *d_octree, hipStream_t stre
 #endif
   } else {
     pa->bricks_valid = false;  // (a field that exists but is not kept current -- a pool deeper than any shape -- is stale from here on)
-    if (fresh) pool_grid_build_kernel<<<(unsigned)(kCells / 256), 256, 0, stream>>>(d_octree, grid, serve[0], serve[1]);
-    else pool_grid_update_kernel<<<kUpdateBlocks, kUpdateThreads, 0, stream>>>(d_octree, grid, serve[0], serve[1]);
+    if (fresh) pool_grid_build_kernel<<<(unsigned)(kCells / 256), 256, 0, stream>>>(d_octree, grid, serve[0], serve[1], node0, node0_par);
+    else pool_grid_update_kernel<<<kUpdateBlocks, kUpdateThreads, 0, stream>>>(d_octree, grid, serve[0], serve[1], node0, node0_par);
   }
   SVO_LAUNCH_CHECK();
   *d_grid = grid;

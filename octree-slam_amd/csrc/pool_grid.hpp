@@ -14,7 +14,15 @@
 //    prefix -- or nodes above level B that have children, which no entry refers to;
 //  * a split gives a childless node at level l eight children: the sibling tiles lie inside the key's level-B block
 //    when l >= B; a split at l < B re-labels the whole cube of the split node, so all 8^(B-l) blocks under it are
-//    marked (first frames of a map only).
+//    marked (first frames of a map only);
+//  * NODE 0's colour word, which block marking does NOT cover: every commit with a valid key ends with the root pass Q6
+//    (pool[1] = the mean of the root's eight children, svo.cu's last mip level), whatever octants its keys lie in, and marks
+//    no block for it.  Entries hold that word in two places: the pyramid's level-1 cell 0 (always), and -- while node 0 is
+//    childless -- EVERY grid and pyramid entry under octant 0, all of them (st = 1, node 0's word).  So every refresh rewrites
+//    level-1 cell 0, and compares node 0's word with the one the previous refresh saw (two words in dirty state 0,
+//    kPoolGridNode0Offset, written in turn): a childless node 0 whose word has changed has octant 0's entries rewritten, one
+//    value for all of them (2.4 M entries, 19 MB: only maps whose octant 0 is empty ever pay it, and only in frames that
+//    change the word).  A node 0 that gets children is a split above level B: its cube is marked as above.
 // Every other way of changing a pool (blocking fusion, voxel grids, load / set_nodes / copy / reset / expand)
 // invalidates the grid as a whole; it is rebuilt in full by the next render.  Memory written behind the library's
 // back (hipMemcpy into svoslam_pool.d_data) must be followed by svoslam_pool_touch().
@@ -51,6 +59,7 @@ struct PoolAccel {
   // refresh must neither see nor clear its marks: a refresh leaves the state of a pending deferred commit alone.
   uint32_t *d_dirty[2] = {nullptr, nullptr};
   bool valid = false;         // false: rebuild everything at the next render
+  unsigned node0_served = 0;  // refreshes so far: the parity of kPoolGridNode0Offset's two words
   // deferred commits (svo_build.hip, svo_fuse_commit_deferred / svo_fuse_apply): colour words a commit computes while the
   // previous frame is still being ray-marched; entry = epoch << 32 | word, valid for the commit whose epoch it carries
   DeviceBuffer shadow;
@@ -123,6 +132,8 @@ constexpr int kPoolGridCountOffset = kPoolGridDirtyWords + kPoolGridBlocks;  // 
 // appended so far (commits), and two marks "served up to here" that the refreshes write in turn -- refresh n of a state reads
 // mark[(n + 1) & 1] (what refresh n - 1 served) and writes mark[n & 1]: no launch has to wait for its last workgroup to reset
 // anything, and the grid's update and the bricks' rebuild can share ONE launch -- then the entries
+// two of the three free words behind the count, in state 0 only: node 0's colour word as refresh n saw it, at [n & 1] (see "NODE 0" above)
+constexpr int kPoolGridNode0Offset = kPoolGridCountOffset + 1;
 constexpr int kBrickCountOffset = kPoolGridCountOffset + 4, kBrickMarkOffset = kBrickCountOffset + 1;
 constexpr int kBrickListOffset = kBrickCountOffset + 4;
 constexpr int kBrickListCap = 1 << 20;  // more than this pending = "rebuild every brick" (a commit appends <= its distinct level-9 prefixes)

@@ -46,7 +46,9 @@ def length(v):
     return np.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
 
 
-def march(words, w, h, fov, inv_view, center, size):
+def march(words, w, h, fov, inv_view, center, size, hook=None, pixels=None):
+    """hook(px, py, lod, node, level, target): called for every sample with its LOD, the node its walk ends on and that node's
+    level (the LOD itself where no level stops the walk); pixels: march only these (px, py) -- the default is the whole image"""
     tanf = ctypes.CDLL("libm.so.6").tanf
     tanf.restype, tanf.argtypes = ctypes.c_float, [ctypes.c_float]
     inv = np.asarray(inv_view, F).reshape(16)
@@ -57,47 +59,48 @@ def march(words, w, h, fov, inv_view, center, size):
     size = F(size)
     img = np.zeros((h, w, 4), np.uint8)
     steps = levels = 0
-    for py in range(h):
-        for px in range(w):
-            mx = (F(px) - F(w) / F(2.0)) / F(532.57)
-            my = (F(py) - F(h) / F(2.0)) / F(531.54)
-            d = (mx * x_dir + my * y_dir) + fwd
-            ray = START_DIST * (d * (F(1.0) / length(d)))
-            while True:
-                steps += 1
-                target = origin + ray
-                ray_len = length(ray)
-                depth = ceil_log2_quotient(size, ray_len * pix_scale)
-                node = child = 0
-                c = np.asarray(center, F).copy()
-                t = size
-                for i in range(depth):
-                    x, y, z = bool(target[0] > c[0]), bool(target[1] > c[1]), bool(target[2] > c[2])
-                    node = child + (int(x) + 2 * int(y) + 4 * int(z))
-                    if not (int(words[2 * node]) & FLAG):
-                        depth = i + 1
-                        break
-                    child = int(words[2 * node]) & MASK
-                    t = t / F(2.0)
-                    c[0] += t * F(1 if x else -1)
-                    c[1] += t * F(1 if y else -1)
-                    c[2] += t * F(1 if z else -1)
-                levels += max(depth, 0)
-                val = int(words[2 * node + 1])
-                alpha = (val >> 24) - 127
-                a = F(alpha) / F(127.0)
-                vx, vy, vz = f2u8(a * F(val & 0xFF)), f2u8(a * F((val >> 8) & 0xFF)), f2u8(a * F((val >> 16) & 0xFF))
-                if not (alpha < 127):          # (int)value.w + alpha with value.w == 0 (Q9)
-                    img[py, px] = (vx, vy, vz, 255)
+    for px, py in ((px, py) for py in range(h) for px in range(w)) if pixels is None else pixels:
+        mx = (F(px) - F(w) / F(2.0)) / F(532.57)
+        my = (F(py) - F(h) / F(2.0)) / F(531.54)
+        d = (mx * x_dir + my * y_dir) + fwd
+        ray = START_DIST * (d * (F(1.0) / length(d)))
+        while True:
+            steps += 1
+            target = origin + ray
+            ray_len = length(ray)
+            lod = depth = ceil_log2_quotient(size, ray_len * pix_scale)
+            node = child = 0
+            c = np.asarray(center, F).copy()
+            t = size
+            for i in range(depth):
+                x, y, z = bool(target[0] > c[0]), bool(target[1] > c[1]), bool(target[2] > c[2])
+                node = child + (int(x) + 2 * int(y) + 4 * int(z))
+                if not (int(words[2 * node]) & FLAG):
+                    depth = i + 1
                     break
-                vw = alpha & 0xFF
-                new_dist = size / F(2.0 ** depth)
-                ray = ray * ((ray_len + new_dist) / ray_len)
-                if length(ray) > MAX_RANGE:
-                    with np.errstate(divide="ignore", invalid="ignore"):
-                        sc = F(127.0) / F(vw)
-                        img[py, px] = (f2u8(F(vx) * sc), f2u8(F(vy) * sc), f2u8(F(vz) * sc), 255)
-                    break
+                child = int(words[2 * node]) & MASK
+                t = t / F(2.0)
+                c[0] += t * F(1 if x else -1)
+                c[1] += t * F(1 if y else -1)
+                c[2] += t * F(1 if z else -1)
+            levels += max(depth, 0)
+            if hook is not None:
+                hook(px, py, lod, node, depth, target)
+            val = int(words[2 * node + 1])
+            alpha = (val >> 24) - 127
+            a = F(alpha) / F(127.0)
+            vx, vy, vz = f2u8(a * F(val & 0xFF)), f2u8(a * F((val >> 8) & 0xFF)), f2u8(a * F((val >> 16) & 0xFF))
+            if not (alpha < 127):          # (int)value.w + alpha with value.w == 0 (Q9)
+                img[py, px] = (vx, vy, vz, 255)
+                break
+            vw = alpha & 0xFF
+            new_dist = size / F(2.0 ** depth)
+            ray = ray * ((ray_len + new_dist) / ray_len)
+            if length(ray) > MAX_RANGE:
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    sc = F(127.0) / F(vw)
+                    img[py, px] = (f2u8(F(vx) * sc), f2u8(F(vy) * sc), f2u8(F(vz) * sc), 255)
+                break
     return img, steps, levels
 
 
