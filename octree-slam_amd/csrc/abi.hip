@@ -103,8 +103,7 @@ int svoslam_pool_free(svoslam_pool *pool) {
   if (pool->d_data) SVO_HIP(hipFree(pool->d_data));
   if (pool->d_size) SVO_HIP(hipFree(pool->d_size));
   pool_tracker_destroy(pool);
-  pool->d_data = nullptr; pool->size = 0; pool->capacity = 0;
-  pool->d_size = nullptr; pool->pending = 0; pool->pending_bound = 0;
+  pool_clear_fields(pool);
   return SVOSLAM_OK;
 }
 int svoslam_pool_reset(svoslam_pool *pool, void *stream) {

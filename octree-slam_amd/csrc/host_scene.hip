@@ -39,8 +39,7 @@ static int ceil_log2_of(float q) {
 // ---- Octree -------------------------------------------------------------------------------
 Octree::Octree(const float resolution, const float center[3], const float size) : size_(size), resolution_(resolution) {
   for (int k = 0; k < 3; k++) center_[k] = center[k];
-  pool_.d_data = nullptr; pool_.size = 0; pool_.capacity = 0;
-  pool_.d_size = nullptr; pool_.pending = 0; pool_.pending_bound = 0;
+  svoslam::pool_clear_fields(&pool_);
 }
 
 Octree::~Octree() {

@@ -29,6 +29,7 @@
 #include <algorithm>
 
 #include "pool_grid.hpp"
+#include "pool_state.hpp"
 #include "radix_sort.hpp"
 #include "svo_build.hpp"
 

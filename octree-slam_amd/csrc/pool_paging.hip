@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "pool_grid.hpp"
+#include "pool_state.hpp"
 #include "radix_sort.hpp"
 #include "svo_build.hpp"
 

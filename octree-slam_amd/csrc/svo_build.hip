@@ -24,6 +24,9 @@
 //   fillNodes race on duplicate keys (:684)    lowest point index wins (stable sort)
 //   mipmapNodes: n redundant walks x D (:450)  owner lanes only, node indices saved
 //                                              by the fill walk
+//
+// The rest of the map lives next door: pool_state.hip (the pool's allocation, size bookkeeping, checkpoints), svo_extract.hip (BFS
+// extraction), svo_keyrange.hip (the key-range sharded commit); svo_fuse_internal.hpp is what they share with this file.
 #include <stdlib.h>
 #include <string.h>
 
@@ -35,13 +38,11 @@
 #include "config.hpp"
 #include "pool_grid.hpp"
 #include "svo_build.hpp"
+#include "svo_fuse_internal.hpp"
 #include "stage_timing.hpp"
 #include "wave_rank.hpp"
 
 namespace svoslam {
-
-typedef unsigned long long u64;
-typedef unsigned int u32;
 
 constexpr unsigned char kNotHead = 0xFE;  // sorted element is a duplicate or an invalid key
 constexpr unsigned char kNoSplit = 0xFF;  // path fully exists, nothing to split
@@ -208,20 +209,7 @@ __global__ __launch_bounds__(kKeysThreads) void keys_packed_kernel(const float *
 // ----------------------------------------------------------------------------
 // planning
 // ----------------------------------------------------------------------------
-// number of leading 3-bit levels two distinct depth-D keys share
-__device__ inline int common_levels(u64 a, u64 b, int depth) {
-  const u64 x = a ^ b;  // != 0, < 2^(3D)
-  const int hb = 63 - __clzll((long long)x);
-  return depth - 1 - hb / 3;
-}
-
-__device__ inline bool is_head(const u64 *__restrict__ skey, int j, u64 &key, int &c, int depth) {
-  key = skey[j];
-  const u64 prev = j > 0 ? skey[j - 1] : 1ull;
-  if (key == 1ull || key == prev) return false;
-  c = (prev == 1ull) ? 0 : common_levels(key, prev, depth);
-  return true;
-}
+// (common_levels, is_head, bucket_id: svo_fuse_internal.hpp)
 
 // splitKeys (svo.cu:108-142) for one key: first node on the path without the
 // children flag.  Q3: the last level is examined only when its octant is 7.
@@ -254,7 +242,6 @@ __device__ inline void record_range(int t, int c, int depth, int &lo, int &hi) {
   else { lo = t > c + 1 ? t : c + 1; hi = depth - 1; }
 }
 
-__device__ inline u32 bucket_id(int p, int d) { return (u32)(p * 16 + (d - 1)); }
 
 // Workgroup id -> tile of the sorted key array.  An XCD-aware order -- tile = (id % 8) * ceil(tiles / 8) + id / 8: one
 // contiguous eighth of the Morton-ordered keys, i.e. a compact part of the tree and of the colour image, per XCD and L2 --
@@ -571,24 +558,7 @@ __global__ __launch_bounds__(256) void fill_kernel(const u64 *__restrict__ skey,
   pool[2 * (size_t)node + 1] = out;
 }
 
-// averageChildren (svo.cu:384-441).  Q5: all 8 children always count.
-__device__ inline u32 average_tile(const u32 *__restrict__ pool, u32 child_base) {
-  const uint4 *tile = reinterpret_cast<const uint4 *>(pool + 2 * (size_t)child_base);
-  u32 r = 0, g = 0, b = 0, a = 0;
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    const uint4 v = tile[q];
-    const u32 w1a = v.y, w1b = v.w;
-    r += (w1a & 0xFF) + (w1b & 0xFF);
-    g += ((w1a >> 8) & 0xFF) + ((w1b >> 8) & 0xFF);
-    b += ((w1a >> 16) & 0xFF) + ((w1b >> 16) & 0xFF);
-    const u32 aa = w1a >> 24, ab = w1b >> 24;
-    a = a > aa ? a : aa;
-    a = a > ab ? a : ab;
-  }
-  // float sums / 8.0f of the reference are exact: integer floor division
-  return (r >> 3) + ((g >> 3) << 8) + ((b >> 3) << 16) + (a << 24);
-}
+// (average_tile -- averageChildren, svo.cu:384-441 -- : svo_fuse_internal.hpp)
 
 // the same with agent-scope (sc1) loads: children that another lane of this launch has just stored write-through
 // (mip_straddle2_kernel, tier 1) must not come from a stale line of this CU's L1
@@ -664,11 +634,7 @@ __global__ void mip_root_kernel(u32 *__restrict__ pool, const PlanCounts *__rest
 // __syncthreads() (same-CU visibility).  Only a node whose run crosses the end of its owner's
 // workgroup -- at most one per workgroup and level -- is deferred to a second, single-workgroup launch
 // that handles those "straddlers" deepest level first.  Same values as the level-by-level passes.
-constexpr u32 kNoStraddler = 0xFFFFFFFFu;
-
-constexpr int kFillThreads = 512;  // leaves per workgroup.  Larger: fewer straddlers for the single-workgroup second launch;
-// smaller: more workgroups resident next to the tracker's (which pin 150 CUs).  Measured at cfg3, fill + straddle us:
-// 1024 -> 54 + 20, 512 -> 45 + 23, 256 -> 37 + 32; 2418 / 2481 / 2477 frames/s.
+// (kNoStraddler, kFillThreads: svo_fuse_internal.hpp)
 template <int MAXD>  // levels a lane keeps in registers: 12 for pools of depth <= 12 (57 VGPRs: four workgroups per CU), 16 otherwise (65: three)
 __global__ __launch_bounds__(kFillThreads) void fill_mip_local_kernel(const u64 *__restrict__ skey, const u32 *__restrict__ sidx, int n,
                                                              int depth, const unsigned char *__restrict__ leaf_t,
@@ -1119,374 +1085,41 @@ __global__ __launch_bounds__(256) void commit_apply_kernel(u32 *__restrict__ poo
   if (t0 == 0 && counts->any_valid) pool[1] = (u32)shadow[0];
 }
 
+// key-range sharded commit (svo_keyrange.hip launches it; it is compiled here, with the straddler kernels above: see there).  One
+// workgroup, behind everything else: the colour words of the nodes above the splitter level on the frame's paths from their merged
+// children (mipmapNodes restricted to levels 2 and 1, svo.cu:450-465), the root pass (Q6), the pool's size and its readback, the list of
+// the marked grid blocks
+__global__ __launch_bounds__(256) void keyrange_finish_kernel(u32 *__restrict__ pool, u32 *__restrict__ scal, unsigned long long *__restrict__ top,
+                                                              int *__restrict__ d_size, int32_t *__restrict__ h_sizes, int *__restrict__ d_slot,
+                                                              u32 *__restrict__ dirty) {
+  const int tid = (int)threadIdx.x;
+  const bool ok = scal[1] == 0u;
+  const unsigned long long m2 = *top;
+  if (ok) {
+    if (tid < 64 && ((m2 >> tid) & 1ull)) {
+      const u32 node1 = (u32)tid >> 3, base1 = pool[2 * (size_t)node1] & kMask;
+      const u32 node2 = base1 + ((u32)tid & 7u);
+      pool[2 * (size_t)node2 + 1] = average_tile(pool, pool[2 * (size_t)node2] & kMask);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid < 8 && ((m2 >> (8 * tid)) & 0xFFull)) pool[2 * (size_t)tid + 1] = average_tile(pool, pool[2 * (size_t)tid] & kMask);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+  if (tid == 0) {
+    if (ok && scal[3]) pool[1] = average_tile(pool, 0u);  // Q6
+    const int size_now = ok ? (int)(scal[2] + 8u * scal[0]) : *d_size;
+    *d_size = size_now;
+    if (h_sizes) { const int sl = *d_slot; h_sizes[sl] = size_now; *d_slot = (sl + 1) % 8; }
+    *top = 0ull;
+  }
+  if (dirty) pool_grid_compact(dirty, 256);
+}
+
 // ----------------------------------------------------------------------------
 // host driver
 // ----------------------------------------------------------------------------
-// ---- non-blocking size tracking of the asynchronous fusion ----------------------------------------
-// Every commit copies the new size (4 bytes) to a pinned host slot behind an event.  The next plan polls
-// the events: each completed one makes pool->size current up to that commit and releases its worst-case
-// reservation, so the host learns the true size a frame or two late WITHOUT ever waiting for the device.
-struct PoolTracker {
-  static constexpr int kSlots = 8;  // == the modulus in mip_straddle_kernel
-  int32_t *h_size = nullptr;  // pinned, device-visible [kSlots]: the commit's last kernel stores the new size itself
-  int *d_slot = nullptr;      // device: slot the next commit writes (advances with `next` below, once per commit)
-  int *d_struct = nullptr;    // device: the pool's size as the STRUCTURE chain sees it (svo_fuse_plan_structure; set from d_size by pool_structure_begin)
-  hipEvent_t ev[kSlots];
-  struct InFlight { int slot; int64_t bound; };
-  InFlight q[kSlots];  // oldest first
-  int count = 0, next = 0;
-  int planned_ahead = 0;  // svo_fuse_plan_structure calls whose commit has not been enqueued yet (their reservations must survive pool_sync)
-  uint32_t numbering = 0;  // bumped when every node index changes (pool_adopt_storage): a plan holds indices of the numbering it read
-};
-
-static PoolTracker *tracker_of(svoslam_pool *pool) { return reinterpret_cast<PoolTracker *>(pool->tracker); }
-
-static int tracker_create(svoslam_pool *pool) {
-  if (pool->tracker) return SVOSLAM_OK;
-  PoolTracker *t = new PoolTracker();
-  for (int i = 0; i < PoolTracker::kSlots; i++) t->ev[i] = nullptr;
-  bool ok = hipHostMalloc((void **)&t->h_size, PoolTracker::kSlots * 4, hipHostMallocDefault) == hipSuccess;
-  for (int i = 0; ok && i < PoolTracker::kSlots; i++) ok = hipEventCreateWithFlags(&t->ev[i], hipEventDisableTiming) == hipSuccess;
-  ok = ok && hipMalloc((void **)&t->d_slot, 4) == hipSuccess && memset_sync(t->d_slot, 0, 4) == hipSuccess;
-  ok = ok && hipMalloc((void **)&t->d_struct, 4) == hipSuccess && memset_sync(t->d_struct, 0, 4) == hipSuccess;
-  pool->tracker = t;
-  if (!ok) {  // whatever was created goes away again (events and pinned memory leaked on these paths)
-    (void)hipGetLastError();
-    pool_tracker_destroy(pool);
-    return SVOSLAM_ERR_HIP;
-  }
-  return SVOSLAM_OK;
-}
-
-void pool_tracker_destroy(svoslam_pool *pool) {
-  PoolTracker *t = pool ? tracker_of(pool) : nullptr;
-  if (!t) return;
-  for (int i = 0; i < PoolTracker::kSlots; i++) if (t->ev[i]) (void)hipEventDestroy(t->ev[i]);
-  if (t->h_size) (void)hipHostFree(t->h_size);
-  if (t->d_slot) (void)hipFree(t->d_slot);
-  if (t->d_struct) (void)hipFree(t->d_struct);
-  delete t;
-  pool->tracker = nullptr;
-}
-
-// retire the completed readbacks (wait_all: block until every one has completed)
-static int tracker_poll(svoslam_pool *pool, bool wait_all) {
-  PoolTracker *t = tracker_of(pool);
-  if (!t) return SVOSLAM_OK;
-  while (t->count > 0) {
-    const PoolTracker::InFlight f = t->q[0];
-    if (wait_all) SVO_HIP(hipEventSynchronize(t->ev[f.slot]));
-    else {
-      const hipError_t e = hipEventQuery(t->ev[f.slot]);
-      if (e == hipErrorNotReady) { (void)hipGetLastError(); break; }
-      SVO_HIP(e);
-    }
-    pool->size = t->h_size[f.slot];
-    pool->pending_bound -= f.bound;
-    if (pool->pending_bound < 0) pool->pending_bound = 0;
-    if (pool->pending > 0) pool->pending -= 1;
-    for (int i = 1; i < t->count; i++) t->q[i - 1] = t->q[i];
-    t->count--;
-  }
-  return SVOSLAM_OK;
-}
-
-// before a commit is enqueued: its last kernel stores the new size into h_size[next], which must not be the slot of a
-// readback the host has not retired yet (with 8 readbacks in flight the 9th commit overwrote the oldest
-// un-polled entry and pool->size jumped ahead and stepped back until the next drain)
-static int tracker_make_room(svoslam_pool *pool) {
-  PoolTracker *t = tracker_of(pool);
-  if (!t || t->count < PoolTracker::kSlots) return SVOSLAM_OK;
-  SVO_HIP(hipEventSynchronize(t->ev[t->q[0].slot]));  // the oldest readback is long done in practice
-  return tracker_poll(pool, false);
-}
-
-// after a commit has been enqueued on `stream`
-static int tracker_push(svoslam_pool *pool, int64_t bound, hipStream_t stream) {
-  PoolTracker *t = tracker_of(pool);
-  if (!t) return SVOSLAM_OK;
-  if (t->count == PoolTracker::kSlots) {  // ring full: the oldest readback is long done in practice
-    SVO_HIP(hipEventSynchronize(t->ev[t->q[0].slot]));
-    SVO_TRY(tracker_poll(pool, false));
-  }
-  const int slot = t->next;
-  t->next = (t->next + 1) % PoolTracker::kSlots;
-  (void)slot;  // h_size[slot] is stored by mip_straddle_kernel (no copy operation between the commit and the next render)
-  SVO_HIP(hipEventRecord(t->ev[slot], stream));
-  t->q[t->count].slot = slot;
-  t->q[t->count].bound = bound;
-  t->count++;
-  return SVOSLAM_OK;
-}
-
-int pool_sync(svoslam_pool *pool, hipStream_t stream) {
-  if (!pool) return SVOSLAM_ERR_INVALID_ARG;
-  if (tracker_of(pool) && tracker_of(pool)->count > 0) {  // the last commit's readback is the exact size
-    SVO_TRY(tracker_poll(pool, true));
-  } else if (pool->pending > 0 && pool->d_size) {
-    int32_t sz = 0;
-    SVO_HIP(hipMemcpyAsync(&sz, pool->d_size, 4, hipMemcpyDeviceToHost, stream));
-    SVO_HIP(hipStreamSynchronize(stream));
-    pool->size = sz;
-  }
-  pool->pending = 0;
-  // what tracker_poll left of pending_bound is the reservation of plans that have no commit yet: zero unless the
-  // structure chain is ahead of its commits
-  if (!tracker_of(pool) || tracker_of(pool)->planned_ahead == 0) pool->pending_bound = 0;
-  return SVOSLAM_OK;
-}
-
-static int ensure_device_size(svoslam_pool *pool, hipStream_t stream) {
-  if (pool->d_size) return SVOSLAM_OK;
-  SVO_HIP(hipMalloc((void **)&pool->d_size, 4));
-  SVO_HIP(hipMemcpyAsync(pool->d_size, &pool->size, 4, hipMemcpyHostToDevice, stream));
-  SVO_HIP(hipStreamSynchronize(stream));
-  return tracker_create(pool);
-}
-
-static int grow_pool(svoslam_pool *pool, int64_t need_nodes, hipStream_t stream, int64_t live_nodes = 0) {
-  if (need_nodes > (int64_t)kMask + 1) return SVOSLAM_ERR_POOL_LIMIT;
-  if (need_nodes <= pool->capacity) return SVOSLAM_OK;
-  SVO_TRY(pool_sync(pool, stream));  // the copy below needs the exact size
-  // live_nodes > size: tiles that plans of the structure chain have written ahead of their commits move along
-  const int64_t copy_nodes = live_nodes > pool->size ? (live_nodes < pool->capacity ? live_nodes : pool->capacity) : pool->size;
-  int64_t cap = (int64_t)pool->capacity * 2;
-  if (cap < need_nodes) cap = need_nodes;
-  if (cap > (int64_t)kMask + 1) cap = (int64_t)kMask + 1;
-  u32 *fresh = nullptr;
-  SVO_HIP(hipMalloc((void **)&fresh, (size_t)cap * 8));
-  if (pool->d_data && copy_nodes > 0)
-    SVO_HIP(hipMemcpyAsync(fresh, pool->d_data, (size_t)copy_nodes * 8, hipMemcpyDeviceToDevice, stream));
-  SVO_HIP(hipStreamSynchronize(stream));
-  pool_accel_rebind(pool->d_data, fresh);
-  if (pool->d_data) SVO_HIP(hipFree(pool->d_data));
-  pool->d_data = fresh;
-  pool->capacity = (int32_t)cap;
-  return SVOSLAM_OK;
-}
-
-int pool_init(svoslam_pool *pool, int32_t capacity_nodes, hipStream_t stream) {
-  if (!pool) return SVOSLAM_ERR_INVALID_ARG;
-  if (capacity_nodes < 8) capacity_nodes = 8;
-  pool->d_data = nullptr; pool->size = 0; pool->capacity = 0;
-  pool->d_size = nullptr; pool->pending = 0; pool->pending_bound = 0; pool->tracker = nullptr;
-  SVO_TRY(grow_pool(pool, capacity_nodes, stream));
-  pool_accel_register(pool);
-  SVO_HIP(hipMemsetAsync(pool->d_data, 0, 64, stream));  // initOctree, svo.cu:24-31
-  pool->size = 8;
-  return ensure_device_size(pool, stream);
-}
-
-// ---- growing the root ("a correct expandBySize that re-roots the GPU pool") -------------
-// The reference's Octree::expandBySize (octree.cpp:362-378) multiplies size_ and, for a GPU-backed root,
-// moves nothing (Q16): the old nodes then describe the wrong region.  Re-rooting the linear tree is local:
-// the 8 children of the old root (nodes 0..7) move to a fresh tile at the end of the pool, nodes 0..7
-// become the children of the NEW root -- all empty except the octant that holds the old root, which gets
-// the children flag, the index of that tile and the mean colour its mip pass would give it.  Every other
-// node keeps its index, so nothing below has to change.
-__global__ void reroot_kernel(u32 *__restrict__ pool, int *__restrict__ d_size, int n0, int octant) {
-  __shared__ uint2 old[8];
-  uint2 *nodes = reinterpret_cast<uint2 *>(pool);
-  if (threadIdx.x < 8) {
-    old[threadIdx.x] = nodes[threadIdx.x];
-    nodes[n0 + threadIdx.x] = old[threadIdx.x];
-  }
-  __syncthreads();
-  if (threadIdx.x < 8) nodes[threadIdx.x] = make_uint2(0u, 0u);  // initOctree, svo.cu:24-31
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    nodes[octant] = make_uint2(kFlag | ((u32)n0 & kMask), average_tile(pool, (u32)n0));
-    if (d_size) *d_size = n0 + 8;
-  }
-}
-
-// One doubling of the root cube towards `toward` (per axis: the side on which toward lies relative to the
-// centre).  center / edge are updated to the new root; the caller fuses with max_depth + 1 from now on to keep
-// its resolution.  Blocking.
-int pool_expand(svoslam_pool *pool, float center[3], float *edge, const float toward[3], hipStream_t stream) {
-  if (!pool || !pool->d_data || !center || !edge || !toward || !(*edge > 0.0f)) return SVOSLAM_ERR_INVALID_ARG;
-  SVO_HIP(hipDeviceSynchronize());
-  SVO_TRY(pool_sync(pool, stream));
-  if ((int64_t)pool->size + 8 > (int64_t)kMask + 1) return SVOSLAM_ERR_POOL_LIMIT;
-  SVO_TRY(grow_pool(pool, (int64_t)pool->size + 8, stream));
-  // the old root becomes the child on the side AWAY from the growth: octant bit = old centre > new centre
-  int octant = 0;
-  float nc[3];
-  for (int k = 0; k < 3; k++) {
-    const bool grow_plus = toward[k] > center[k];
-    nc[k] = center[k] + (grow_plus ? *edge : -*edge);
-    if (center[k] > nc[k]) octant |= 1 << k;
-  }
-  reroot_kernel<<<1, 64, 0, stream>>>(pool->d_data, pool->d_size, pool->size, octant);
-  SVO_LAUNCH_CHECK();
-  pool_accel_invalidate(pool, 0, false);  // every cell of the level grid now lies one level deeper (the words are the same ones)
-  SVO_HIP(hipStreamSynchronize(stream));
-  pool->size += 8;
-  for (int k = 0; k < 3; k++) center[k] = nc[k];
-  *edge = *edge * 2.0f;
-  return SVOSLAM_OK;
-}
-
-// back to initOctree (8 zeroed root children) keeping the allocation.  Blocking.
-int pool_reset(svoslam_pool *pool, hipStream_t stream) {
-  if (!pool || !pool->d_data) return SVOSLAM_ERR_INVALID_ARG;
-  SVO_HIP(hipDeviceSynchronize());
-  SVO_TRY(pool_sync(pool, stream));  // drains the size tracker
-  SVO_HIP(memset_sync(pool->d_data, 0, 64));
-  pool_accel_invalidate(pool, -1);
-  pool->size = 8; pool->pending = 0; pool->pending_bound = 0;
-  if (tracker_of(pool)) tracker_of(pool)->planned_ahead = 0;  // plans of the structure chain whose commit never came (an error mid-run) hold no reservation any more
-  if (pool->d_size) SVO_HIP(hipMemcpy(pool->d_size, &pool->size, 4, hipMemcpyHostToDevice));
-  return SVOSLAM_OK;
-}
-
-int pool_reserve(svoslam_pool *pool, int32_t capacity_nodes, hipStream_t stream) {
-  if (!pool) return SVOSLAM_ERR_INVALID_ARG;
-  return grow_pool(pool, capacity_nodes, stream);
-}
-
-// ---- what pool_compact.hip needs of the bookkeeping above ----------------------------------------
-// plans of the structure chain whose commit has not been enqueued yet (they hold node indices of the present numbering)
-int pool_planned_ahead(svoslam_pool *pool) { return tracker_of(pool) ? tracker_of(pool)->planned_ahead : 0; }
-
-// The pool's nodes now live in `fresh` (size_nodes of them, room for capacity_nodes): the march acceleration data follows
-// the pointer as in grow_pool and is invalidated for a full rebuild, the old allocation is freed, host and device size
-// and the reservations are reset as in pool_set_nodes.  The caller has synchronised the device and the pool.
-int pool_adopt_storage(svoslam_pool *pool, uint32_t *fresh, int32_t size_nodes, int32_t capacity_nodes, hipStream_t stream) {
-  SVO_TRY(ensure_device_size(pool, stream));
-  tracker_of(pool)->numbering++;  // a svo_fuse_plan without its commit yet is void from here on (commit_impl refuses it)
-  pool_accel_rebind(pool->d_data, fresh);
-  u32 *old = pool->d_data;
-  pool->d_data = fresh;
-  pool->capacity = capacity_nodes;
-  pool->size = size_nodes;
-  pool->pending = 0; pool->pending_bound = 0;
-  pool_accel_invalidate(pool, 0, false);  // the same words under new indices
-  pool_accel_trim_shadow(pool);           // a deferred-commit shadow sized for a larger capacity goes back too
-  if (old) SVO_HIP(hipFree(old));
-  SVO_HIP(hipMemcpy(pool->d_size, &pool->size, 4, hipMemcpyHostToDevice));
-  return SVOSLAM_OK;
-}
-
-// size bookkeeping after nodes were appended behind pool->size by something other than a fusion (pool_paging.hip: graft)
-int pool_set_size(svoslam_pool *pool, int32_t size_nodes, hipStream_t stream) {
-  SVO_TRY(ensure_device_size(pool, stream));
-  pool->size = size_nodes;
-  pool->pending = 0; pool->pending_bound = 0;
-  SVO_HIP(hipMemcpy(pool->d_size, &pool->size, 4, hipMemcpyHostToDevice));
-  return SVOSLAM_OK;
-}
-
-// ---- checkpoint / resume -------------------------------------------------------------
-// The pool IS the reference's linear tree (the layout OctreeNode::pushToGPU assembles, octree.cpp:41-79:
-// 2-word nodes, 0x40000000 children flag, 30-bit child index), so a checkpoint is the node words behind
-// a 64-byte header.  The reference's own (de)serialiser is unfinished (addToLinearTree never sets the
-// flag, octree.cpp:138-160), so there is no reference byte stream to match.
-struct PoolFileHeader {
-  char magic[8];        // "SVOPOOL1"
-  uint32_t version;     // 1
-  int32_t num_nodes;
-  float center[3];
-  float edge_length;    // half edge of the root cube
-  int32_t max_depth;
-  uint32_t reserved;
-  uint64_t checksum;    // FNV-1a over the node words
-  uint8_t pad[16];
-};
-static_assert(sizeof(PoolFileHeader) == 64, "header is 64 bytes");
-
-static uint64_t fnv1a_words(const u32 *w, size_t n) {
-  uint64_t h = 1469598103934665603ull;
-  for (size_t i = 0; i < n; i++) h = (h ^ (uint64_t)w[i]) * 1099511628211ull;
-  return h;
-}
-
-int pool_save(svoslam_pool *pool, const char *path, const float center[3], float edge, int depth, hipStream_t stream) {
-  if (!pool || !path || !center || !pool->d_data) return SVOSLAM_ERR_INVALID_ARG;
-  SVO_HIP(hipDeviceSynchronize());  // commits may be in flight on other streams
-  SVO_TRY(pool_sync(pool, stream));
-  const size_t words = 2 * (size_t)pool->size;
-  std::vector<u32> host(words);
-  SVO_HIP(hipMemcpy(host.data(), pool->d_data, words * 4, hipMemcpyDeviceToHost));
-  PoolFileHeader h;
-  memset(&h, 0, sizeof(h));
-  memcpy(h.magic, "SVOPOOL1", 8);
-  h.version = 1; h.num_nodes = pool->size;
-  h.center[0] = center[0]; h.center[1] = center[1]; h.center[2] = center[2];
-  h.edge_length = edge; h.max_depth = depth;
-  h.checksum = fnv1a_words(host.data(), words);
-  FILE *f = fopen(path, "wb");
-  if (!f) return SVOSLAM_ERR_IO;
-  const bool ok = fwrite(&h, sizeof(h), 1, f) == 1 && (words == 0 || fwrite(host.data(), 4, words, f) == words);
-  return (fclose(f) == 0 && ok) ? SVOSLAM_OK : SVOSLAM_ERR_IO;
-}
-
-// Replaces the pool's contents by num_nodes host nodes (a linear tree in the reference format): validates the child
-// pointers, waits for everything in flight, and resets ALL size bookkeeping -- host size, device-resident size,
-// reservations of asynchronous fusions.  Blocking.
-int pool_set_nodes(svoslam_pool *pool, const uint32_t *h_words, int32_t num_nodes, hipStream_t stream) {
-  if (!pool || !h_words || num_nodes < 8 || (num_nodes & 7) != 0) return SVOSLAM_ERR_INVALID_ARG;
-  for (size_t i = 0; i < (size_t)num_nodes; i++) {  // every child tile must lie inside the pool
-    const u32 w0 = h_words[2 * i];
-    if ((w0 & kFlag) && ((w0 & kMask) + 8u > (u32)num_nodes || ((w0 & kMask) & 7u))) return SVOSLAM_ERR_FORMAT;
-  }
-  SVO_HIP(hipDeviceSynchronize());
-  if (!pool->d_data) SVO_TRY(pool_init(pool, num_nodes, stream));
-  SVO_TRY(pool_sync(pool, stream));
-  SVO_TRY(grow_pool(pool, num_nodes, stream));
-  SVO_HIP(hipMemcpy(pool->d_data, h_words, (size_t)num_nodes * 8, hipMemcpyHostToDevice));
-  pool_accel_invalidate(pool);
-  pool->size = num_nodes;
-  pool->pending = 0; pool->pending_bound = 0;
-  if (tracker_of(pool)) tracker_of(pool)->planned_ahead = 0;
-  if (pool->d_size) SVO_HIP(hipMemcpy(pool->d_size, &pool->size, 4, hipMemcpyHostToDevice));
-  return SVOSLAM_OK;
-}
-
-// dst becomes a byte-identical replica of src (same nodes, same size, at least the same capacity).  Blocking: waits
-// for the device (either pool may have work in flight on any stream).
-int pool_copy(svoslam_pool *dst, svoslam_pool *src, hipStream_t stream) {
-  if (!dst || !src || dst == src || !src->d_data) return SVOSLAM_ERR_INVALID_ARG;
-  SVO_HIP(hipDeviceSynchronize());
-  SVO_TRY(pool_sync(src, stream));
-  if (!dst->d_data) SVO_TRY(pool_init(dst, src->capacity, stream));
-  SVO_TRY(pool_sync(dst, stream));
-  if (dst->capacity < src->capacity) {
-    dst->size = 0;  // nothing worth copying over to the larger allocation
-    SVO_TRY(grow_pool(dst, src->capacity, stream));
-  }
-  SVO_HIP(hipMemcpy(dst->d_data, src->d_data, (size_t)src->size * 8, hipMemcpyDeviceToDevice));
-  pool_accel_invalidate(dst);
-  SVO_HIP(hipDeviceSynchronize());
-  dst->size = src->size;
-  dst->pending = 0; dst->pending_bound = 0;
-  SVO_TRY(ensure_device_size(dst, stream));
-  SVO_HIP(hipMemcpy(dst->d_size, &dst->size, 4, hipMemcpyHostToDevice));
-  return SVOSLAM_OK;
-}
-
-int pool_load(svoslam_pool *pool, const char *path, float center[3], float *edge, int *depth, hipStream_t stream) {
-  if (!pool || !path) return SVOSLAM_ERR_INVALID_ARG;
-  FILE *f = fopen(path, "rb");
-  if (!f) return SVOSLAM_ERR_IO;
-  PoolFileHeader h;
-  if (fread(&h, sizeof(h), 1, f) != 1 || memcmp(h.magic, "SVOPOOL1", 8) != 0 || h.version != 1 || h.num_nodes < 8 ||
-      (h.num_nodes & 7) != 0) {
-    fclose(f);
-    return SVOSLAM_ERR_FORMAT;
-  }
-  const size_t words = 2 * (size_t)h.num_nodes;
-  std::vector<u32> host(words);
-  const bool ok = fread(host.data(), 4, words, f) == words;
-  fclose(f);
-  if (!ok || fnv1a_words(host.data(), words) != h.checksum) return SVOSLAM_ERR_FORMAT;
-  SVO_TRY(pool_set_nodes(pool, host.data(), h.num_nodes, stream));
-  if (center) { center[0] = h.center[0]; center[1] = h.center[1]; center[2] = h.center[2]; }
-  if (edge) *edge = h.edge_length;
-  if (depth) *depth = h.max_depth;
-  return SVOSLAM_OK;
-}
-
 static int reserve_common(svoslam_workspace *ws, int n, int depth) {
   const size_t nn = (size_t)(n > 0 ? n : 1);
   SVO_TRY(ws->keys_a.reserve(nn * 8));
@@ -1503,14 +1136,7 @@ static int reserve_common(svoslam_workspace *ws, int n, int depth) {
   return SVOSLAM_OK;
 }
 
-// layout of ws->small (u32 words): [0,256) totals | [256,513) bucket_base | [520..) PlanCounts | [640] any_valid | [648] n0 | [656] plan ticket (any_valid and the ticket start at 0 and are left at 0 by every plan)
-static inline u32 *small_totals(svoslam_workspace *ws) { return ws->small.as<u32>(); }
-static inline u32 *small_bucket_base(svoslam_workspace *ws) { return ws->small.as<u32>() + 256; }
-static inline PlanCounts *small_counts(svoslam_workspace *ws) { return reinterpret_cast<PlanCounts *>(ws->small.as<u32>() + 520); }
-static inline int *small_any(svoslam_workspace *ws) { return reinterpret_cast<int *>(ws->small.as<u32>() + 640); }
-static inline u32 *small_n0(svoslam_workspace *ws) { return ws->small.as<u32>() + 648; }  // deferred commit: first new tile
-static inline unsigned *small_ticket(svoslam_workspace *ws) { return ws->small.as<u32>() + 656; }  // plan_scan_finish_kernel's arrival count
-static inline unsigned *small_strad_ticket(svoslam_workspace *ws) { return ws->small.as<u32>() + 664; }  // mip_straddle2_kernel's (zero between launches)
+// (layout of ws->small and its small_* accessors, max_records: svo_fuse_internal.hpp)
 
 // keys of the n inputs are in ws->keys_a
 // The blocking insert's sort (round 5): one packed word per point where key and index fit 64 bits -- and the key ALONE on the
@@ -1588,16 +1214,6 @@ static int svo_insert(svoslam_workspace *ws, int n, int depth, svoslam_pool *poo
   return SVOSLAM_OK;
 }
 
-// worst-case number of split records of one call: at depth d at most min(8^d, n) distinct prefixes can be
-// split (d < D), plus at most n octant-7 leaves (Q4)
-static int64_t max_records(int n, int depth) {
-  int64_t r = n;
-  for (int d = 1; d < depth; d++) {
-    const int64_t cells = d >= 11 ? (int64_t)1 << 62 : (int64_t)1 << (3 * d);
-    r += cells < n ? cells : n;
-  }
-  return r;
-}
 
 // Asynchronous fusion: same kernels up to the plan, then every split in one launch (split_all_kernel), no
 // readback.  The host only knows an upper bound of the pool size; capacity is kept ahead of it.
@@ -1784,27 +1400,6 @@ int svo_fuse_merge_sorted(const unsigned long long *const *d_keys, const uint32_
   return SVOSLAM_OK;
 }
 
-__global__ void pool_structure_begin_kernel(int *__restrict__ d_struct, const int *__restrict__ d_size) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) *d_struct = *d_size;
-}
-
-// The structure chain (for callers that do not render every frame: one rank of a frame-sharded session).  A plan reads
-// only the pool's STRUCTURE words (children flags and links), and those are final once the splits of the previous frame
-// are in -- its leaf blend and mip levels write colour words only.  svo_fuse_plan_structure = plan + split_all (links
-// included) in one go, numbering its tiles from a size that follows the PLANS (d_struct); it needs no commit to have
-// finished, only the previous svo_fuse_plan_structure (same stream, or ordered by the caller).  The commits -- leaf kernel +
-// straddlers, as after svo_fuse_split_early -- follow in order on another stream.  Frames then cost the longer of the two
-// chains instead of their sum.  The caller keeps a ray march of frame k away from the structure of frame k+1: no
-// svo_fuse_plan_structure(k+1) before the march of frame k is done.  pool_structure_begin: once, after everything
-// earlier on the pool has completed in stream order (d_struct := the pool's size).
-int pool_structure_begin(svoslam_pool *pool, hipStream_t stream) {
-  if (!pool) return SVOSLAM_ERR_INVALID_ARG;
-  if (pool->size == 0) SVO_TRY(pool_init(pool, 8, stream));
-  SVO_TRY(ensure_device_size(pool, stream));
-  pool_structure_begin_kernel<<<1, 64, 0, stream>>>(tracker_of(pool)->d_struct, pool->d_size);
-  SVO_LAUNCH_CHECK();
-  return SVOSLAM_OK;
-}
 
 // svoslam_pool_compact re-indexed the pool after this workspace's plan read it: the node indices the plan left in the workspace
 // (leaf_f, leaf_start, rec_front) mean other nodes now, or none (a shrunk allocation)
@@ -1906,11 +1501,11 @@ int svo_fuse_split_early(svoslam_workspace *ws, int n, int depth, svoslam_pool *
   return SVOSLAM_OK;
 }
 
-// keyrange (key-range sharded commit, below): a deferred commit of this rank's slice of the frame -- the workspace's sorted arrays hold the
+// keyrange (key-range sharded commit, svo_keyrange.hip): a deferred commit of this rank's slice of the frame -- the workspace's sorted arrays hold the
 // slice followed by padding, *n_live its length --, without marks for the ray march's grid / bricks (keyrange_mark_kernel makes them, from
 // ALL keys), without the pool's new size and without the size readback (svo_fuse_keyrange_apply: keyrange_finish_kernel, tracker_push)
-static int commit_impl(svoslam_workspace *ws, const uint8_t *d_colors, int n, int depth, svoslam_pool *pool, bool deferred,
-                       hipStream_t stream, const int *n_live = nullptr) {
+int commit_impl(svoslam_workspace *ws, const uint8_t *d_colors, int n, int depth, svoslam_pool *pool, bool deferred,
+                hipStream_t stream, const int *n_live) {
   const bool keyrange = n_live != nullptr;
   if (!ws || !pool || n < 0 || (n > 0 && !d_colors)) return SVOSLAM_ERR_INVALID_ARG;
   if (pool_shadow_pending(pool)) return SVOSLAM_ERR_INVALID_ARG;  // a deferred commit of this pool has not been applied
@@ -2075,603 +1670,6 @@ int svo_from_voxel_grid(svoslam_workspace *ws, const float *d_centers, const flo
   // Q20 (svo.cu:601-602,629): the reference sorts the keys alone, so sorted key i
   // stays paired with colour i -> color_by_position
   return svo_insert(ws, n, depth, pool, d_colors, true, true, stats, stream, tk, idx_bits);
-}
-
-// ----------------------------------------------------------------------------
-// extraction (svo.cu:498-582, 699-745): level-synchronous BFS with an
-// order-preserving compaction per level
-// ----------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void bfs_count_kernel(const u32 *__restrict__ pool, const u64 *__restrict__ parents,
-                                                        int num, unsigned char *__restrict__ mask8,
-                                                        u32 *__restrict__ tile_cnt) {
-  __shared__ u32 tmp[4];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  u32 cntv = 0;
-  if (i < num) {
-    const u64 key = parents[i];
-    const int d = (63 - __clzll((long long)key)) / 3;
-    bool has_children = true;
-    u32 pointer = 0;
-    for (int l = d - 1; l >= 0; l--) {  // getOccupiedChildren :515-520
-      pointer += (u32)(key >> (3 * l)) & 7u;
-      const u32 w0 = pool[2 * (size_t)pointer];
-      has_children = (w0 & kFlag) != 0;
-      pointer = w0 & kMask;
-    }
-    u32 m = 0;
-    if (has_children) {
-      const uint4 *tile = reinterpret_cast<const uint4 *>(pool + 2 * (size_t)pointer);
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const uint4 v = tile[q];
-        if ((v.y >> 24) > 127u) m |= 1u << (2 * q);
-        if ((v.w >> 24) > 127u) m |= 1u << (2 * q + 1);
-      }
-    }
-    mask8[i] = (unsigned char)m;
-    cntv = __popc(m);
-  }
-  u32 total;
-  (void)block256_exclusive_scan(cntv, tmp, total);
-  if (threadIdx.x == 0) tile_cnt[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(256) void bfs_emit_kernel(const u64 *__restrict__ parents, int num,
-                                                       const unsigned char *__restrict__ mask8,
-                                                       const u32 *__restrict__ tile_prefix, u64 *__restrict__ children) {
-  __shared__ u32 tmp[4];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const u32 m = i < num ? mask8[i] : 0u;
-  u32 total;
-  u32 pos = tile_prefix[blockIdx.x] + block256_exclusive_scan(__popc(m), tmp, total);
-  if (i < num) {
-    const u64 key = parents[i];
-#pragma unroll
-    for (int k = 0; k < 8; k++)
-      if (m & (1u << k)) children[pos++] = (key << 3) + (u64)k;
-  }
-}
-
-// voxelGridFromKeys, svo.cu:538-582
-__global__ __launch_bounds__(256) void voxel_grid_from_keys_kernel(const u32 *__restrict__ pool, const u64 *__restrict__ keys,
-                                                                   int num, float cx, float cy, float cz, float edge,
-                                                                   float4 *__restrict__ centers, float4 *__restrict__ colors) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= num) return;
-  const u64 key = keys[i];
-  const int d = (63 - __clzll((long long)key)) / 3;
-  u32 node = 0, child = 0;
-  for (int l = d - 1; l >= 0; l--) {
-    const u32 p = (u32)(key >> (3 * l)) & 7u;
-    node = child + p;
-    child = pool[2 * (size_t)node] & kMask;
-    edge /= 2.0f;
-    cx += edge * ((p & 1u) ? 1 : -1);
-    cy += edge * ((p & 2u) ? 1 : -1);
-    cz += edge * ((p & 4u) ? 1 : -1);
-  }
-  const u32 val = pool[2 * (size_t)node + 1];
-  centers[i] = make_float4(cx, cy, cz, 1.0f);
-  colors[i] = make_float4((float)(val & 0xFF) / 255.0f, (float)((val >> 8) & 0xFF) / 255.0f,
-                          (float)((val >> 16) & 0xFF) / 255.0f, (float)((val >> 24) & 0xFF) / 255.0f);
-}
-
-int extract_voxel_grid(svoslam_workspace *ws, const svoslam_pool *pool, int depth, const float center[3], float edge,
-                       float **d_centers, float **d_colors, int32_t *n_out, hipStream_t stream) {
-  if (!ws || !pool || !d_centers || !d_colors || !n_out) return SVOSLAM_ERR_INVALID_ARG;
-  if (depth < 1 || depth > SVOSLAM_MAX_DEPTH) return SVOSLAM_ERR_DEPTH;
-  *d_centers = nullptr; *d_colors = nullptr; *n_out = 0;
-  if (pool->size == 0) return SVOSLAM_OK;
-  if (pool->pending > 0) SVO_HIP(hipStreamSynchronize(stream));  // (size itself is not needed by the BFS)
-  SVO_TRY(ws->reserve_small());  // (zeroed when created: any_valid and the plan's arrival ticket start at zero)
-  SVO_TRY(ws->bfs_a.reserve(8));
-  const u64 one = 1;
-  SVO_HIP(hipMemcpyAsync(ws->bfs_a.ptr, &one, 8, hipMemcpyHostToDevice, stream));
-  SVO_HIP(hipStreamSynchronize(stream));
-  svoslam::DeviceBuffer *cur = &ws->bfs_a, *nxt = &ws->bfs_b;
-  int num = 1;
-  for (int lvl = 0; lvl < depth && num > 0; lvl++) {
-    const int tiles = (int)cdiv(num, 256);
-    SVO_TRY(ws->bfs_mask.reserve((size_t)num));
-    SVO_TRY(ws->tile_hist.reserve((size_t)(tiles + 1) * 4));
-    bfs_count_kernel<<<tiles, 256, 0, stream>>>(pool->d_data, cur->as<u64>(), num, ws->bfs_mask.as<unsigned char>(), ws->tile_hist.as<u32>());
-    row_scan_rows1(ws->tile_hist.as<u32>(), tiles, small_totals(ws), stream);
-    unsigned next_num = 0;
-    SVO_HIP(hipMemcpyAsync(&next_num, small_totals(ws), 4, hipMemcpyDeviceToHost, stream));
-    SVO_HIP(hipStreamSynchronize(stream));
-    if (next_num > 0) {
-      SVO_TRY(nxt->reserve((size_t)next_num * 8));
-      bfs_emit_kernel<<<tiles, 256, 0, stream>>>(cur->as<u64>(), num, ws->bfs_mask.as<unsigned char>(), ws->tile_hist.as<u32>(), nxt->as<u64>());
-      SVO_LAUNCH_CHECK();
-    }
-    svoslam::DeviceBuffer *t = cur; cur = nxt; nxt = t;
-    num = (int)next_num;
-  }
-  if (num <= 0) return SVOSLAM_OK;
-  float *ce = nullptr, *co = nullptr;
-  SVO_HIP(hipMalloc((void **)&ce, (size_t)num * 16));
-  SVO_HIP(hipMalloc((void **)&co, (size_t)num * 16));
-  voxel_grid_from_keys_kernel<<<cdiv(num, 256), 256, 0, stream>>>(pool->d_data, cur->as<u64>(), num, center[0], center[1], center[2], edge,
-                                                                  reinterpret_cast<float4 *>(ce), reinterpret_cast<float4 *>(co));
-  SVO_LAUNCH_CHECK();
-  SVO_HIP(hipStreamSynchronize(stream));
-  *d_centers = ce; *d_colors = co; *n_out = num;
-  return SVOSLAM_OK;
-}
-
-
-// ----------------------------------------------------------------------------
-// key-range sharded commit (protocol pinned on the CPU by tests/test_keyrange_gloo.py)
-// ----------------------------------------------------------------------------
-// The plan + commit of ONE frame cut across `world` ranks by key range instead of being replicated on every rank.  Every rank holds a
-// byte-identical replica of the pool and the frame's sorted keys (sorted by their owners and all-gathered: svo_fuse_export_sorted /
-// svo_fuse_merge_sorted).  Two calls per frame and rank, ONE all-gather between them:
-//   svo_fuse_keyrange_commit  the rank's slice of the sorted keys -- the keys under a contiguous run of level-3 prefixes holding about
-//                             n / world keys (keyrange_bounds_kernel: every rank computes the same cuts) -- is planned (svo.cu:179-237)
-//                             and committed (:239-465) by the unchanged kernels as a DEFERRED commit: new tiles beyond the pool's size
-//                             in the rank's own numbering, colour words in the shadow array, nothing a replica could not still
-//                             discard.  keyrange_pack_* then writes the rank's DELTA: its (pass, depth) bucket sizes, its new tiles
-//                             (16 words each, links still in local numbering), the frontier nodes its pass-0 records link from,
-//                             {node, colour word} of every existing node it changed, the bricks whose siblings its splits created;
-//   [all-gather of the deltas -- the caller's: RCCL, or a table of precomputed deltas for an emulated rank]
-//   svo_fuse_keyrange_apply   numbering: the reference numbers the new tiles of a pass by the rank of their key among the pass's sorted
-//                             unique keys = bucket-major, key order inside a bucket; slices are key ranges, so rank s's records of
-//                             bucket b follow those of ranks < s: global index = bucket base + sum of the lower ranks' counts + local
-//                             rank in the bucket -- one table of world x 256 offsets (keyrange_setup_kernel).  Every delta (the own one
-//                             included) is written to its global place; the marks of the ray march's grid / bricks are made from ALL the
-//                             frame's keys against this replica's own dirty state (ranks render different frames: their dirty states
-//                             differ); the colour words of the nodes above the splitter level -- shared by several ranks' paths -- are
-//                             recomputed from the merged children, level by level, then the root pass (Q6); size and size readback.
-// Frames whose splits reach ABOVE the splitter level (a node of level 1 or 2 without children: the first frames of a map, new territory)
-// make several ranks plan the SAME records (the prefix of such a record lies on paths of more than one slice) and create the same tiles:
-// every delta lists its records above the splitter level by key, keyrange_setup_kernel ranks them in the ranks' UNION (the reference's
-// order inside their buckets) and clears their tiles, and the apply writes of such a tile only the nodes a rank actually filled -- a
-// level-3 node has one owner; the shallower ones get the same link from everybody and their colour words from the recomputation.
-constexpr int kKrLevel = 3;
-constexpr int kKrMaxWorld = 16;
-constexpr int kKrHeader = 512;       // words: scalars, then the 256 bucket sizes at [256, 512)
-constexpr int kKrSibCap = 8192;      // entries
-constexpr int kKrShallowCap = 1024;  // keys (two words each)
-constexpr int kKrTopCap = 128;       // records above the splitter level: {key (two words), local record, bucket}; a rank has at most 8 + 64
-constexpr int kKrTop0 = kKrHeader + kKrSibCap + 2 * kKrShallowCap;
-constexpr int kKrTiles0 = kKrTop0 + 4 * kKrTopCap;  // first word of the tiles
-enum { kKrMagic = 0, kKrRecords = 1, kKrWords = 2, kKrLinks = 3, kKrSib = 4, kKrShallow = 5, kKrAnyValid = 6, kKrOverflow = 7, kKrSliceKeys = 8,
-       kKrN0 = 9, kKrUsed = 10, kKrCapacity = 11, kKrDepth = 12, kKrTop = 13 };
-enum { kKrOverflowed = 2, kKrMismatch = 4 };
-constexpr u32 kKrEmpty1 = 127u << 24;  // word1 of a node splitNodes has just created (svo.cu:269-275)
-__host__ __device__ inline size_t kr_bid0(u32 records) { return (size_t)kKrTiles0 + 16 * (size_t)records; }
-__host__ __device__ inline size_t kr_links0(u32 records) { return kr_bid0(records) + (records + 3u) / 4u; }
-__host__ __device__ inline size_t kr_words0(u32 records, u32 links) { return kr_links0(records) + links; }
-
-// window of rank `rank`: win[0] = first, win[1] = end, win[2] = length of its slice of the sorted keys (invalid keys -- key 1 -- sort first
-// and belong to nobody).  Cut r lies at the end of the level-L run that holds key number r x valid / world.
-__global__ void keyrange_bounds_kernel(const u64 *__restrict__ skey, int n, int depth, int rank, int world, int *__restrict__ win) {
-  const int r = (int)threadIdx.x;
-  auto first_at_least = [&](int lo, int hi, u64 bound, int shift) {  // first j in [lo, hi) with (skey[j] >> shift) >= bound
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if ((skey[mid] >> shift) < bound) lo = mid + 1; else hi = mid; }
-    return lo;
-  };
-  const int v0 = first_at_least(0, n, 2ull, 0);
-  const long long nv = n - v0;
-  int b = v0;
-  if (r >= world) b = n;
-  else if (r > 0) {
-    const int i = v0 + (int)((long long)r * nv / world);
-    if (i > v0) { const int sh = 3 * (depth - kKrLevel); b = first_at_least(i, n, (skey[i - 1] >> sh) + 1ull, sh); }
-  }
-  if (r <= world) win[4 + r] = b;
-  __syncthreads();
-  if (r == 0) { const int lo = win[4 + rank], hi = win[4 + rank + 1]; win[0] = lo; win[1] = hi; win[2] = hi - lo; }
-}
-
-__global__ __launch_bounds__(256) void keyrange_slice_kernel(const u64 *__restrict__ skey, const u32 *__restrict__ sidx, int n,
-                                                             const int *__restrict__ win, u64 *__restrict__ out_key, u32 *__restrict__ out_idx) {
-  const int j = (int)(blockIdx.x * 256u + threadIdx.x);
-  if (j >= n) return;
-  const int lo = win[0], len = win[2];
-  out_key[j] = j < len ? skey[lo + j] : 1ull;  // the slice at the front, padding (invalid keys) behind it
-  out_idx[j] = j < len ? sidx[lo + j] : 0u;
-}
-
-__global__ __launch_bounds__(256) void keyrange_pack_header_kernel(u32 *__restrict__ delta, long long capacity_words, const u32 *__restrict__ bucket_base,
-                                                                   const PlanCounts *__restrict__ counts, const u32 *__restrict__ n0_saved,
-                                                                   const int *__restrict__ win, int depth) {
-  const int t = (int)threadIdx.x;
-  delta[256 + t] = bucket_base[t + 1] - bucket_base[t];
-  if (t == 0) {
-    const u32 R = (u32)counts->total_records, links = (u32)(counts->pass_start[1] - counts->pass_start[0]);
-    delta[kKrMagic] = 0x4B52414Eu;
-    delta[kKrRecords] = R; delta[kKrWords] = 0u; delta[kKrLinks] = links; delta[kKrSib] = 0u; delta[kKrShallow] = 0u; delta[kKrTop] = 0u;
-    delta[kKrAnyValid] = (u32)counts->any_valid; delta[kKrSliceKeys] = (u32)win[2]; delta[kKrN0] = *n0_saved; delta[kKrDepth] = (u32)depth;
-    delta[kKrCapacity] = capacity_words > 0xFFFFFFFFll ? 0xFFFFFFFFu : (u32)capacity_words;
-    const bool fits = (long long)kr_words0(R, links) <= capacity_words;
-    delta[kKrOverflow] = fits ? 0u : 1u;
-    delta[kKrUsed] = (u32)kr_words0(R, links);
-  }
-}
-
-// the new tiles (one lane per node), the records' buckets, the pass-0 records' frontier nodes, and what the receivers' brick / grid marks
-// need from the records: the bricks whose node this commit created (their childless siblings get their lines: pool_grid.hip
-// brick_siblings) and the keys of splits above the grid's block level (they re-label a whole cube)
-__global__ __launch_bounds__(256) void keyrange_pack_tiles_kernel(u32 *__restrict__ delta, const u32 *__restrict__ pool,
-                                                                  const unsigned long long *__restrict__ shadow, u32 epoch,
-                                                                  const u64 *__restrict__ rec_key, const u32 *__restrict__ rec_front,
-                                                                  const unsigned char *__restrict__ rec_pass, int brick_shift) {
-  if (delta[kKrOverflow]) return;
-  const u32 R = delta[kKrRecords], links = delta[kKrLinks], n0 = delta[kKrN0];
-  unsigned char *bid = reinterpret_cast<unsigned char *>(delta + kr_bid0(R));
-  for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < 8 * (size_t)R; i += (size_t)gridDim.x * 256u) {
-    const u32 r = (u32)(i >> 3), q = (u32)(i & 7u);
-    const u32 node = n0 + 8u * r + q;
-    const unsigned long long sh = shadow[node];
-    const u32 w0 = pool[2 * (size_t)node], w1 = (u32)(sh >> 32) == epoch ? (u32)sh : pool[2 * (size_t)node + 1];
-    reinterpret_cast<uint2 *>(delta + kKrTiles0)[i] = make_uint2(w0, w1);
-    if (q == 0u) {
-      const u64 key = rec_key[r];
-      const int d = (63 - __clzll((long long)key)) / 3, pass = rec_pass[r];
-      bid[r] = (unsigned char)bucket_id(pass, d);
-      if (r < links) delta[kr_links0(R) + r] = rec_front[r];
-      if (d < kKrLevel) {  // a record several ranks may hold: listed by key for the union numbering
-        const u32 pos = atomicAdd(&delta[kKrTop], 1u);
-        if (pos < (u32)kKrTopCap) {
-          u32 *e = delta + kKrTop0 + 4 * pos;
-          e[0] = (u32)key; e[1] = (u32)(key >> 32); e[2] = r; e[3] = bucket_id(pass, d);
-        }
-      }
-      if (d < kPoolGridBlockLevel) {
-        const u32 pos = atomicAdd(&delta[kKrShallow], 1u);
-        if (pos < (u32)kKrShallowCap) reinterpret_cast<u64 *>(delta + kKrHeader + kKrSibCap)[pos] = key;
-      }
-      if (brick_shift >= 0 && d == brick_node_level(brick_shift) && pass >= 1) {
-        u32 x = 0, y = 0, z = 0;
-        for (int k = 1; k <= d; k++) {
-          const u32 oct = (u32)(key >> (3 * (d - k))) & 7u;
-          x = (x << 1) | (oct & 1u); y = (y << 1) | ((oct >> 1) & 1u); z = (z << 1) | (oct >> 2);
-        }
-        const u32 org = brick_window_origin(brick_shift) >> 2;
-        x -= org; y -= org; z -= org;
-        if ((x | y | z) < (kBrickWindowCells >> 2)) {
-          const u32 pos = atomicAdd(&delta[kKrSib], 1u);
-          if (pos < (u32)kKrSibCap) delta[kKrHeader + pos] = brick_list_entry(x, y, z);
-        }
-      }
-    }
-  }
-}
-
-// {node, colour word} of the EXISTING nodes (below the pool's size) this commit changed: the leaf kernel's per-workgroup lists, then the
-// straddler list (workgroups past the lists take 2048 entries each).  A workgroup counts, reserves with one atomic, writes.
-__global__ __launch_bounds__(256) void keyrange_pack_words_kernel(u32 *__restrict__ delta, const unsigned long long *__restrict__ shadow,
-                                                                  const u32 *__restrict__ apply_nodes, int fill_tiles, int list_cap,
-                                                                  const u32 *__restrict__ strad, int strad_first, int strad_end) {
-  if (delta[kKrOverflow]) return;
-  __shared__ u32 wave_cnt[4], base_s;
-  const u32 R = delta[kKrRecords], links = delta[kKrLinks], n0 = delta[kKrN0], cap = delta[kKrCapacity];
-  const int t = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const bool lists = t < fill_tiles;
-  const u32 *src; u32 cnt, stride;
-  if (lists) { src = apply_nodes + (size_t)t * list_cap; cnt = apply_nodes[(size_t)fill_tiles * list_cap + t]; stride = 1u; }
-  else {
-    const long long first = strad_first + (long long)(t - fill_tiles) * 2048;
-    src = strad + 2 * first; stride = 2u;
-    const long long left = (long long)strad_end - first;
-    cnt = left <= 0 ? 0u : (left < 2048 ? (u32)left : 2048u);
-  }
-  auto wanted = [&](u32 i) { if (i >= cnt) return false; const u32 node = src[(size_t)i * stride]; return node != kNoStraddler && node < n0; };
-  u32 mine = 0;
-  for (u32 i = (u32)tid; i < cnt; i += 256u) mine += wanted(i) ? 1u : 0u;
-  u32 incl = mine;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const u32 v = __shfl_up(incl, o); if (lane >= o) incl += v; }
-  if (lane == 63) wave_cnt[wave] = incl;
-  __syncthreads();
-  u32 before = 0, total = 0;
-  for (int w = 0; w < 4; w++) { if (w < wave) before += wave_cnt[w]; total += wave_cnt[w]; }
-  if (tid == 0) base_s = total ? atomicAdd(&delta[kKrWords], total) : 0u;
-  __syncthreads();
-  if (!total) return;
-  const size_t w0 = kr_words0(R, links);
-  if (w0 + 2 * ((size_t)base_s + total) > (size_t)cap) { if (tid == 0) delta[kKrOverflow] = 1u; return; }
-  u32 pos = base_s + before + incl - mine;
-  for (u32 i = (u32)tid; i < cnt; i += 256u)
-    if (wanted(i)) {
-      const u32 node = src[(size_t)i * stride];
-      delta[w0 + 2 * (size_t)pos] = node;
-      delta[w0 + 2 * (size_t)pos + 1] = (u32)shadow[node];
-      pos++;
-    }
-  if (tid == 0) atomicMax(&delta[kKrUsed], (u32)(w0 + 2 * ((size_t)base_s + total)));
-}
-
-struct KrDeltas { const u32 *d[kKrMaxWorld]; };
-
-// numbering: table[s][b] = what to add to rank s's local record rank in bucket b (depth >= 3) to get its place in the reference's order;
-// topmap[s] = {count, then (local record, place) pairs} for rank s's records above the splitter level, ranked in the ranks' union; the
-// union's tiles cleared; scal[0] = records of all ranks (shared ones once), [1] = status flags, [2] = first new tile, [3] = any valid key
-constexpr int kKrTopMax = kKrMaxWorld * kKrTopCap;
-__global__ __launch_bounds__(256) void keyrange_setup_kernel(KrDeltas D, int world, int *__restrict__ table, u32 *__restrict__ topmap,
-                                                             u32 *__restrict__ scal, u32 *__restrict__ pool) {
-  __shared__ unsigned tmp[4];
-  __shared__ u64 top_key[kKrTopMax];
-  __shared__ unsigned short top_bs[kKrTopMax];   // bucket | rank << 8
-  __shared__ unsigned char top_first[kKrTopMax];
-  __shared__ u32 top_base[kKrMaxWorld + 1], union_cnt[256];
-  const int b = (int)threadIdx.x;
-  u32 tot = 0, flags = 0, any = 0;
-  union_cnt[b] = 0u;
-  if (b == 0) {
-    u32 run = 0;
-    for (int s = 0; s < world; s++) { top_base[s] = run; const u32 c = D.d[s][kKrTop]; run += c < (u32)kKrTopCap ? c : (u32)kKrTopCap; }
-    top_base[world] = run;
-  }
-  __syncthreads();
-  const int M = (int)top_base[world];
-  for (int s = 0; s < world; s++) {
-    if (D.d[s][kKrOverflow] || D.d[s][kKrTop] > (u32)kKrTopCap) flags |= kKrOverflowed;
-    if (D.d[s][kKrN0] != D.d[0][kKrN0] || D.d[s][kKrMagic] != 0x4B52414Eu) flags |= kKrMismatch;
-    any |= D.d[s][kKrAnyValid];
-    const int cnt = (int)(top_base[s + 1] - top_base[s]);
-    for (int i = b; i < cnt; i += 256) {
-      const u32 *e = D.d[s] + kKrTop0 + 4 * i;
-      top_key[top_base[s] + i] = ((u64)e[1] << 32) | e[0];
-      top_bs[top_base[s] + i] = (unsigned short)(e[3] | ((u32)s << 8));
-    }
-  }
-  __syncthreads();
-  // the union: an entry is its record's FIRST occurrence when no earlier entry holds the same (bucket, key)
-  for (int e = b; e < M; e += 256) {
-    bool first = true;
-    for (int f = 0; f < e && first; f++) first = !(top_key[f] == top_key[e] && (top_bs[f] & 255u) == (top_bs[e] & 255u));
-    top_first[e] = first ? 1 : 0;
-    if (first) atomicAdd(&union_cnt[top_bs[e] & 255u], 1u);
-  }
-  __syncthreads();
-  const int d = (b & 15) + 1;  // bucket_id(p, d) = 16 p + d - 1
-  if (d < kKrLevel) tot = union_cnt[b];
-  else for (int s = 0; s < world; s++) tot += D.d[s][256 + b];
-  unsigned total;
-  const u32 gbase = block256_exclusive_scan(tot, tmp, total);
-  __shared__ u32 gbase_s[256];
-  gbase_s[b] = gbase;
-  u32 lower = 0;
-  for (int s = 0; s < world; s++) {
-    const u32 c = D.d[s][256 + b];
-    unsigned ltot;
-    const u32 lbase = block256_exclusive_scan(c, tmp, ltot);
-    table[s * 256 + b] = (int)(gbase + lower) - (int)lbase;
-    lower += c;
-  }
-  __syncthreads();
-  const u32 n0 = D.d[0][kKrN0];
-  for (int e = b; e < M; e += 256) {
-    const u32 bk = top_bs[e] & 255u, s = top_bs[e] >> 8;
-    u32 rank = 0;  // first occurrences of the bucket with a smaller key
-    for (int f = 0; f < M; f++) rank += (top_first[f] && (top_bs[f] & 255u) == bk && top_key[f] < top_key[e]) ? 1u : 0u;
-    const u32 place = gbase_s[bk] + rank;
-    const u32 slot = (u32)e - top_base[s];
-    topmap[s * (1 + 2 * kKrTopCap) + 1 + 2 * slot] = D.d[s][kKrTop0 + 4 * slot + 2];
-    topmap[s * (1 + 2 * kKrTopCap) + 2 + 2 * slot] = place;
-    if (top_first[e] && !flags) {  // the shared tile starts as eight empty children; the ranks then write what they filled
-      uint4 *tile = reinterpret_cast<uint4 *>(pool + 2 * ((size_t)n0 + 8 * (size_t)place));
-      const uint4 init = make_uint4(0u, kKrEmpty1, 0u, kKrEmpty1);
-      tile[0] = init; tile[1] = init; tile[2] = init; tile[3] = init;
-    }
-  }
-  if (b < world) topmap[b * (1 + 2 * kKrTopCap)] = top_base[b + 1] - top_base[b];
-  if (flags) atomicOr(&scal[1], flags);
-  if (b == 0) { scal[0] = total; scal[2] = n0; scal[3] = any; }
-}
-
-// every delta to its global place (blockIdx.y = the delta's rank): tiles with their links renumbered, the pass-0 links, the colour words
-// of existing nodes, and the record-borne marks (sibling ring, cubes of shallow splits) into this replica's dirty state
-__global__ __launch_bounds__(256) void keyrange_apply_kernel(KrDeltas D, const int *__restrict__ table, const u32 *__restrict__ topmap,
-                                                             const u32 *__restrict__ scal, u32 *__restrict__ pool, u32 *__restrict__ dirty) {
-  if (scal[1]) return;  // overflowed / mismatching deltas: nothing is applied (svo_fuse_keyrange_status reports it)
-  const int s = (int)blockIdx.y;
-  const u32 *delta = D.d[s];
-  const int *T = table + s * 256;
-  const u32 *tm = topmap + s * (1 + 2 * kKrTopCap);
-  const u32 R = delta[kKrRecords], links = delta[kKrLinks], words = delta[kKrWords], n0 = delta[kKrN0];
-  const unsigned char *bid = reinterpret_cast<const unsigned char *>(delta + kr_bid0(R));
-  auto shared_record = [&](u32 r) { return (int)(bid[r] & 15u) + 1 < kKrLevel; };
-  auto place = [&](u32 r) {
-    if (shared_record(r)) {  // ranked in the ranks' union (a handful per frame, in the first frames of a map)
-      const u32 cnt = tm[0];
-      for (u32 i = 0; i < cnt; i++) if (tm[1 + 2 * i] == r) return tm[2 + 2 * i];
-      return 0u;
-    }
-    return (u32)((int)r + T[bid[r]]);
-  };
-  const size_t stride = (size_t)gridDim.x * 256u, t0 = (size_t)blockIdx.x * 256u + threadIdx.x;
-  for (size_t i = t0; i < 8 * (size_t)R; i += stride) {
-    const u32 r = (u32)(i >> 3), q = (u32)(i & 7u);
-    uint2 w = reinterpret_cast<const uint2 *>(delta + kKrTiles0)[i];
-    if (shared_record(r) && w.x == 0u && w.y == kKrEmpty1) continue;  // a node of a shared tile this rank did not fill
-    if (w.x & kFlag) w.x = kFlag | ((n0 + 8u * place(((w.x & kMask) - n0) >> 3)) & kMask);
-    reinterpret_cast<uint2 *>(pool)[(size_t)n0 + 8 * (size_t)place(r) + q] = w;
-  }
-  for (size_t r = t0; r < links; r += stride) pool[2 * (size_t)delta[kr_links0(R) + r]] = kFlag | ((n0 + 8u * place((u32)r)) & kMask);
-  const size_t w0 = kr_words0(R, links);
-  for (size_t i = t0; i < words; i += stride) pool[2 * (size_t)delta[w0 + 2 * i] + 1] = delta[w0 + 2 * i + 1];
-  if (dirty) {
-    const u32 sib = delta[kKrSib] < (u32)kKrSibCap ? delta[kKrSib] : (u32)kKrSibCap;
-    for (size_t i = t0; i < sib; i += stride) brick_sibling_list(dirty, delta[kKrHeader + i]);
-    const u32 sh = delta[kKrShallow];
-    if (sh > (u32)kKrShallowCap) {  // more shallow splits than the list holds: every block is stale
-      for (size_t i = t0; i < (size_t)kPoolGridDirtyWords; i += stride) dirty[i] = 0xFFFFFFFFu;
-    } else {
-      for (size_t i = t0; i < sh; i += stride) {
-        const u64 key = reinterpret_cast<const u64 *>(delta + kKrHeader + kKrSibCap)[i];
-        pool_grid_mark(dirty, key, (63 - __clzll((long long)key)) / 3);
-      }
-    }
-  }
-}
-
-// the marks of the ray march's level grid and occupancy bricks from ALL keys of the frame (as the leaf kernel makes them for the keys it
-// commits: pool_grid.hpp), and the level-2 prefixes that occur (top[0..1]: a 64-bit mask) for the shared nodes' colour words
-__global__ __launch_bounds__(256) void keyrange_mark_kernel(const u64 *__restrict__ skey, int n, int depth, u32 *__restrict__ dirty, int brick_shift,
-                                                            unsigned long long *__restrict__ top) {
-  __shared__ u32 brick_cnt, brick_base;
-  __shared__ unsigned long long mask_s;
-  const int tid = (int)threadIdx.x, j = (int)(blockIdx.x * 256u + threadIdx.x);
-  if (tid == 0) { brick_cnt = 0u; mask_s = 0ull; }
-  __syncthreads();
-  u64 key = 1; int c = 0;
-  const bool head = j < n && is_head(skey, j, key, c, depth);
-  if (head && c < 2) atomicOr(&mask_s, 1ull << ((key >> (3 * (depth - 2))) & 63ull));
-  if (dirty && head && c < kPoolGridBlockLevel) pool_grid_mark(dirty, key, depth);
-  const bool bricks_on = dirty != nullptr && brick_shift >= 0 && depth >= brick_node_level(brick_shift);
-  u32 entry = 0, off = 0;
-  const bool mine = bricks_on && brick_mark_test(dirty, head && c < brick_node_level(brick_shift), key, depth, brick_shift, entry);
-  const unsigned long long bm = __ballot(mine);
-  if (bm) {
-    const int leader = __ffsll((long long)bm) - 1;
-    u32 woff = 0;
-    if ((tid & 63) == leader) woff = atomicAdd(&brick_cnt, (u32)__popcll(bm));
-    off = (u32)__shfl((int)woff, leader) + (u32)__popcll(bm & ((1ull << (tid & 63)) - 1ull));
-  }
-  __syncthreads();
-  if (tid == 0) {
-    if (brick_cnt) brick_base = brick_ring_reserve(dirty, brick_cnt);
-    if (mask_s) atomicOr(top, mask_s);
-  }
-  __syncthreads();
-  if (mine) brick_ring_store(dirty, brick_base + off, entry);
-}
-
-// one workgroup, behind everything else: the colour words of the nodes above the splitter level on the frame's paths from their merged
-// children (mipmapNodes restricted to levels 2 and 1, svo.cu:450-465), the root pass (Q6), the pool's size and its readback, the list of
-// the marked grid blocks
-__global__ __launch_bounds__(256) void keyrange_finish_kernel(u32 *__restrict__ pool, u32 *__restrict__ scal, unsigned long long *__restrict__ top,
-                                                              int *__restrict__ d_size, int32_t *__restrict__ h_sizes, int *__restrict__ d_slot,
-                                                              u32 *__restrict__ dirty) {
-  const int tid = (int)threadIdx.x;
-  const bool ok = scal[1] == 0u;
-  const unsigned long long m2 = *top;
-  if (ok) {
-    if (tid < 64 && ((m2 >> tid) & 1ull)) {
-      const u32 node1 = (u32)tid >> 3, base1 = pool[2 * (size_t)node1] & kMask;
-      const u32 node2 = base1 + ((u32)tid & 7u);
-      pool[2 * (size_t)node2 + 1] = average_tile(pool, pool[2 * (size_t)node2] & kMask);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid < 8 && ((m2 >> (8 * tid)) & 0xFFull)) pool[2 * (size_t)tid + 1] = average_tile(pool, pool[2 * (size_t)tid] & kMask);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-  if (tid == 0) {
-    if (ok && scal[3]) pool[1] = average_tile(pool, 0u);  // Q6
-    const int size_now = ok ? (int)(scal[2] + 8u * scal[0]) : *d_size;
-    *d_size = size_now;
-    if (h_sizes) { const int sl = *d_slot; h_sizes[sl] = size_now; *d_slot = (sl + 1) % 8; }
-    *top = 0ull;
-  }
-  if (dirty) pool_grid_compact(dirty, 256);
-}
-
-static int kr_scratch(svoslam_workspace *ws, int n) {  // slice arrays + window / table / scalars (zeroed once)
-  SVO_TRY(ws->kr_keys.reserve((size_t)n * 8));
-  SVO_TRY(ws->kr_idx.reserve((size_t)n * 4));
-  if (ws->kr_small.bytes < 65536) {
-    SVO_TRY(ws->kr_small.reserve(65536));
-    SVO_HIP(memset_sync(ws->kr_small.ptr, 0, ws->kr_small.bytes));
-  }
-  return SVOSLAM_OK;
-}
-static inline int *kr_win(svoslam_workspace *ws) { return ws->kr_small.as<int>(); }                       // [0..3] window, [4..4+world] cuts
-static inline u32 *kr_scal(svoslam_workspace *ws) { return ws->kr_small.as<u32>() + 64; }                 // setup scalars
-static inline unsigned long long *kr_top(svoslam_workspace *ws) { return reinterpret_cast<unsigned long long *>(ws->kr_small.as<u32>() + 96); }
-static inline int *kr_table(svoslam_workspace *ws) { return ws->kr_small.as<int>() + 128; }               // [world][256]
-static inline u32 *kr_topmap(svoslam_workspace *ws) { return ws->kr_small.as<u32>() + 128 + kKrMaxWorld * 256; }  // [world][1 + 2 x kKrTopCap]
-
-int svo_fuse_keyrange_commit(svoslam_workspace *ws, const unsigned long long *d_keys, const uint32_t *d_idx, const uint8_t *d_colors, int n,
-                             int depth, svoslam_pool *pool, int rank, int world, uint32_t *d_delta, long long delta_bytes, hipStream_t stream) {
-  if (!ws || !pool || !d_delta || n <= 0 || !d_keys || !d_idx || !d_colors) return SVOSLAM_ERR_INVALID_ARG;
-  if (world < 1 || world > kKrMaxWorld || rank < 0 || rank >= world) return SVOSLAM_ERR_INVALID_ARG;
-  if (depth < kKrLevel + 3 || depth > SVOSLAM_MAX_DEPTH) return SVOSLAM_ERR_DEPTH;
-  if (delta_bytes < (long long)(kKrTiles0 + 64) * 4) return SVOSLAM_ERR_INVALID_ARG;
-  SVO_TRY(kr_scratch(ws, n));
-  int *win = kr_win(ws);
-  keyrange_bounds_kernel<<<1, 64, 0, stream>>>(d_keys, n, depth, rank, world, win);
-  keyrange_slice_kernel<<<cdiv(n, 256), 256, 0, stream>>>(d_keys, d_idx, n, win, ws->kr_keys.as<u64>(), ws->kr_idx.as<u32>());
-  SVO_LAUNCH_CHECK();
-  SVO_TRY(svo_fuse_adopt_sorted(ws, ws->kr_keys.as<u64>(), ws->kr_idx.as<u32>(), n, depth));
-  SVO_TRY(svo_fuse_plan(ws, n, depth, pool, stream));
-  SVO_TRY(commit_impl(ws, d_colors, n, depth, pool, true, stream, win + 2));
-  // the delta
-  unsigned long long *shadow = nullptr;
-  u32 epoch = 0;
-  SVO_TRY(pool_shadow_current(pool, &shadow, &epoch));
-  int brick_shift = -1;
-  (void)pool_accel_dirty_bitmap(pool, 0, depth, &brick_shift);  // (the shape this pool's bricks have, or will have, at this depth)
-  if (depth < brick_node_level(brick_shift < 0 ? 0 : brick_shift)) brick_shift = -1;
-  const int fill_tiles = ws->deferred_tiles;
-  const long long rmax = max_records(n, depth);
-  int tile_blocks = (int)cdiv(8 * rmax, 256);
-  if (tile_blocks > 4096) tile_blocks = 4096;
-  const int strad_first = fill_tiles, strad_end = depth * fill_tiles;
-  const int strad_blocks = (int)cdiv((long long)strad_end - strad_first, 2048);
-  keyrange_pack_header_kernel<<<1, 256, 0, stream>>>(d_delta, delta_bytes / 4, small_bucket_base(ws), small_counts(ws), small_n0(ws), win, depth);
-  keyrange_pack_tiles_kernel<<<tile_blocks, 256, 0, stream>>>(d_delta, pool->d_data, shadow, epoch, ws->rec_key.as<u64>(), ws->rec_front.as<u32>(),
-                                                              ws->rec_pass.as<unsigned char>(), brick_shift);
-  keyrange_pack_words_kernel<<<fill_tiles + strad_blocks, 256, 0, stream>>>(d_delta, shadow, ws->apply_nodes.as<u32>(), fill_tiles, kFillThreads * depth,
-                                                                            ws->strad.as<u32>(), strad_first, strad_end);
-  SVO_LAUNCH_CHECK();
-  pool_shadow_end(pool);
-  ws->deferred_pool = nullptr;
-  ws->keyrange_pool = pool;
-  return SVOSLAM_OK;
-}
-
-int svo_fuse_keyrange_apply(svoslam_workspace *ws, const unsigned long long *d_keys, int n, int depth, svoslam_pool *pool,
-                            const uint32_t *const *d_deltas, int world, hipStream_t stream) {
-  if (!ws || !pool || !d_deltas || !d_keys || n <= 0 || world < 1 || world > kKrMaxWorld) return SVOSLAM_ERR_INVALID_ARG;
-  if (ws->keyrange_pool != pool) return SVOSLAM_ERR_INVALID_ARG;  // svo_fuse_keyrange_commit of this frame has not run on this workspace
-  ws->keyrange_pool = nullptr;
-  KrDeltas D;
-  for (int s = 0; s < kKrMaxWorld; s++) D.d[s] = s < world ? d_deltas[s] : nullptr;
-  for (int s = 0; s < world; s++) if (!D.d[s]) return SVOSLAM_ERR_INVALID_ARG;
-  PoolTracker *trk = tracker_of(pool);
-  int brick_shift = -1;
-  u32 *dirty = pool_accel_dirty_bitmap(pool, 0, depth, &brick_shift);  // direct-commit state; nullptr: not a registered pool
-  const long long rmax = max_records(n, depth);
-  int blocks = (int)cdiv(8 * rmax / (world > 1 ? world : 1) + 1, 256);
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 64) blocks = 64;
-  keyrange_setup_kernel<<<1, 256, 0, stream>>>(D, world, kr_table(ws), kr_topmap(ws), kr_scal(ws), pool->d_data);
-  keyrange_apply_kernel<<<dim3((unsigned)blocks, (unsigned)world), 256, 0, stream>>>(D, kr_table(ws), kr_topmap(ws), kr_scal(ws), pool->d_data, dirty);
-  keyrange_mark_kernel<<<cdiv(n, 256), 256, 0, stream>>>(d_keys, n, depth, dirty, brick_shift, kr_top(ws));
-  SVO_TRY(tracker_make_room(pool));
-  keyrange_finish_kernel<<<1, 256, 0, stream>>>(pool->d_data, kr_scal(ws), kr_top(ws), pool->d_size, trk ? trk->h_size : nullptr,
-                                                trk ? trk->d_slot : nullptr, dirty);
-  SVO_LAUNCH_CHECK();
-  pool->pending += 1;
-  return tracker_push(pool, ws->keyrange_bound, stream);
-}
-
-// a svo_fuse_keyrange_commit whose delta is wanted but whose apply will not follow on this pool (the deltas of OTHER ranks, produced on one
-// device for an emulated rank: bench.py --exchange keyrange --emulate-rank): the plan's reservation is released, the pool is as it was
-int svo_fuse_keyrange_discard(svoslam_workspace *ws, svoslam_pool *pool) {
-  if (!ws || !pool || ws->keyrange_pool != pool) return SVOSLAM_ERR_INVALID_ARG;
-  ws->keyrange_pool = nullptr;
-  pool->pending_bound -= ws->keyrange_bound;
-  if (pool->pending_bound < 0) pool->pending_bound = 0;
-  return SVOSLAM_OK;
-}
-
-// flags of the svo_fuse_keyrange_apply calls on this workspace since the last call of this function (blocking; the flags are sticky on
-// the device and cleared here): 0 = every frame applied; kKrOverflowed / kKrMismatch = a frame was NOT applied (the replica
-// is then behind the others)
-int svo_fuse_keyrange_status(svoslam_workspace *ws, int *flags, hipStream_t stream) {
-  if (!ws || !flags || ws->kr_small.bytes == 0) return SVOSLAM_ERR_INVALID_ARG;
-  u32 f = 0;
-  SVO_HIP(hipMemcpyAsync(&f, kr_scal(ws) + 1, 4, hipMemcpyDeviceToHost, stream));
-  SVO_HIP(hipStreamSynchronize(stream));
-  *flags = (int)f;
-  if (f) SVO_HIP(memset_sync(kr_scal(ws) + 1, 0, 4));
-  return SVOSLAM_OK;
 }
 
 }  // namespace svoslam

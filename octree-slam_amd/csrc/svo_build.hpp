@@ -1,29 +1,18 @@
-// svo_build.hpp -- see svo_build.hip
+// svo_build.hpp -- the map: fusion (svo_build.hip), key-range sharded commit (svo_keyrange.hip), extraction (svo_extract.hip), paging
+// (pool_paging.hip), re-indexing (pool_compact.hip), and through pool_state.hpp the pool itself
 #pragma once
 #include "common.hpp"
+#include "pool_state.hpp"
 #include "workspace.hpp"
 
 namespace svoslam {
-int pool_init(svoslam_pool *pool, int32_t capacity_nodes, hipStream_t stream);
-int pool_reserve(svoslam_pool *pool, int32_t capacity_nodes, hipStream_t stream);
-int pool_sync(svoslam_pool *pool, hipStream_t stream);
-int pool_reset(svoslam_pool *pool, hipStream_t stream);
-int pool_expand(svoslam_pool *pool, float center[3], float *edge, const float toward[3], hipStream_t stream);
-void pool_tracker_destroy(svoslam_pool *pool);
-int pool_save(svoslam_pool *pool, const char *path, const float center[3], float edge, int depth, hipStream_t stream);
-int pool_set_nodes(svoslam_pool *pool, const uint32_t *h_words, int32_t num_nodes, hipStream_t stream);
-int pool_copy(svoslam_pool *dst, svoslam_pool *src, hipStream_t stream);
 // out-of-core paging of sub-trees (pool_paging.hip)
 int pool_evict_subtree(svoslam_pool *pool, const uint8_t *path, int levels, const char *file, hipStream_t stream);
 int pool_restore_subtree(svoslam_pool *pool, const char *file, hipStream_t stream);
 int subtree_file_nodes(const char *file, uint32_t **h_words, int32_t *num_nodes);
-// re-indexing (pool_compact.hip) and the bookkeeping it shares with svo_build.hip
+// re-indexing (pool_compact.hip)
 int pool_compact(svoslam_pool *pool, int32_t capacity_nodes, uint32_t *d_old_tile, svoslam_compact_stats *stats, hipStream_t stream);
 int pool_graft_subtree(svoslam_pool *pool, const char *file, hipStream_t stream);
-int pool_planned_ahead(svoslam_pool *pool);
-int pool_adopt_storage(svoslam_pool *pool, uint32_t *fresh, int32_t size_nodes, int32_t capacity_nodes, hipStream_t stream);
-int pool_set_size(svoslam_pool *pool, int32_t size_nodes, hipStream_t stream);
-int pool_load(svoslam_pool *pool, const char *path, float center[3], float *edge, int *depth, hipStream_t stream);
 int svo_from_point_cloud_async(svoslam_workspace *ws, const float *d_points, const uint8_t *d_colors, int n, int depth,
                                svoslam_pool *pool, const float center[3], float edge, hipStream_t stream);
 int svo_fuse_sort(svoslam_workspace *ws, const float *d_points, int n, int depth, const float center[3], float edge,
@@ -31,7 +20,6 @@ int svo_fuse_sort(svoslam_workspace *ws, const float *d_points, int n, int depth
 int svo_fuse_sort_frame(svoslam_workspace *ws, const uint16_t *d_depth, const float *d_pose, int w, int h, float fx, float fy, int depth,
                         const float center[3], float edge, float *d_bbox7, hipStream_t stream);
 int svo_fuse_plan(svoslam_workspace *ws, int n, int depth, svoslam_pool *pool, hipStream_t stream);
-int pool_structure_begin(svoslam_pool *pool, hipStream_t stream);
 int svo_fuse_sort_frame_band(svoslam_workspace *ws, const uint16_t *d_depth, const float *d_pose, int w, int h, float fx, float fy, int depth,
                              const float center[3], float edge, int first_row, int rows, hipStream_t stream);
 int svo_fuse_merge_sorted(const unsigned long long *const *d_keys, const uint32_t *const *d_idx, const int32_t *counts, int lists,

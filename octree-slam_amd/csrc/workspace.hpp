@@ -79,6 +79,7 @@ struct svoslam_workspace {
     keys_a.release(); keys_b.release(); vals_a.release(); vals_b.release(); tile_hist.release(); small.release();
     leaf_t.release(); leaf_f.release(); rec_key.release(); rec_front.release(); path_nodes.release(); strad.release();
     rec_pass.release(); apply_nodes.release(); leaf_rec0.release(); leaf_start.release();
+    kr_keys.release(); kr_idx.release(); kr_small.release();
     bfs_a.release(); bfs_b.release(); bfs_mask.release(); bfs_ptr.release(); misc.release(); scan_tmp.release(); frame_bbox.release();
     if (h_counts) { (void)hipHostFree(h_counts); h_counts = nullptr; }
   }

@@ -729,7 +729,7 @@ class SlamPipeline:
             self.dist.check_mailbox()
 
     def _run_keyrange(self, n, g0, rgbs, timestamps, views, deltas, events, march, outs, skeys, sidx, sevents):
-        """The fusion of a frame-sharded session cut by KEY RANGE (csrc/svo_build.hip "key-range sharded commit"; include/svoslam.h
+        """The fusion of a frame-sharded session cut by KEY RANGE (csrc/svo_keyrange.hip; include/svoslam.h
         svoslam_svo_fuse_keyrange_*): per frame, on two streams,
           C  keyrange_commit -- this rank's slice of the frame's sorted keys planned and committed where no replica sees it, its
              delta packed -- then the all-gather of the ranks' deltas; frame k+1's may run beside the march of frame k;

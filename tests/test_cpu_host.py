@@ -61,6 +61,21 @@ def test_product_never_imports_oracle():
                         raise AssertionError("%s:%d references the oracle: %s" % (f, ln, line.strip()))
 
 
+def test_workspace_release_all_releases_every_device_buffer():
+    """every DeviceBuffer member of struct svoslam_workspace (csrc/workspace.hpp) is released by release_all(): a buffer that is
+    not leaks when its workspace is destroyed"""
+    text = open(os.path.join(ROOT, "octree-slam_amd", "csrc", "workspace.hpp")).read()
+    struct = text[text.index("struct svoslam_workspace {"):]
+    members = []
+    for decl in re.findall(r"^\s*svoslam::DeviceBuffer\s+([^;]+);", struct, re.M):
+        members += [name.strip() for name in decl.split(",")]
+    assert len(members) >= 20 and all(re.fullmatch(r"[a-z_0-9]+", m) for m in members), members
+    body = struct[struct.index("void release_all()"):]
+    body = body[:body.index("\n  }") + 1]
+    missing = [m for m in members if not re.search(r"\b%s\.release\(\)" % m, body)]
+    assert not missing, "release_all() does not release: %s" % ", ".join(missing)
+
+
 # ---- oracle vs independent float64 numpy restatements -----------------------
 def test_oracle_bilateral_vs_float64(oracle):
     rng = np.random.default_rng(0)

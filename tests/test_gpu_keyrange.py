@@ -1,4 +1,4 @@
-"""Key-range sharded fusion on the GPU (csrc/svo_build.hip "key-range sharded commit"; the protocol is pinned on the CPU by
+"""Key-range sharded fusion on the GPU (csrc/svo_keyrange.hip; the protocol is pinned on the CPU by
 tests/test_keyrange_gloo.py): `world` replicas of one pool in ONE process stand for the ranks -- every frame each of them plans and commits
 its slice of the frame's sorted keys (svoslam_svo_fuse_keyrange_commit), the deltas are "all-gathered" (the tensors are simply shared), and
 every replica applies all of them (svoslam_svo_fuse_keyrange_apply).  After every frame every replica must equal, byte for byte, the pool
