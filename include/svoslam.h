@@ -37,7 +37,8 @@ typedef enum {
   SVOSLAM_ERR_HIP = -3,
   SVOSLAM_ERR_OOM = -4,
   SVOSLAM_ERR_DEPTH = -5,      /* max_depth outside [1, SVOSLAM_MAX_DEPTH] */
-  SVOSLAM_ERR_POOL_LIMIT = -6, /* pool would exceed 2^30 nodes (30-bit child index) */
+  SVOSLAM_ERR_POOL_LIMIT = -6, /* pool would exceed 2^30 nodes (30-bit child index); svoslam_extract_surface_mesh: the surface has
+                                  more than (2^31 - 1) / 4 faces (its 4 x faces corner keys are sorted with an int count) */
   SVOSLAM_ERR_TRACKING_LOST = -7,
   SVOSLAM_ERR_IO = -8,         /* file could not be opened / read / written */
   SVOSLAM_ERR_FORMAT = -9      /* file is not what it should be (magic, size, checksum, structure) */
@@ -336,6 +337,33 @@ int svoslam_extract_voxel_grid(svoslam_workspace *ws, const svoslam_pool *pool, 
                                const float center[3], float edge_length, float **d_centers, float **d_colors,
                                int32_t *n_out, void *stream);
 int svoslam_free(void *d_ptr);
+
+/* The map's surface at max_depth as a welded quad mesh (no reference counterpart; specification in DESIGN.md section 12).
+ * Cells: exactly those svoslam_extract_voxel_grid(pool, max_depth) returns -- every node on the path has alpha > 127, every
+ * node above the cell has children; below the fused depth the mip alpha gives a coarser surface.  With x, y, z in [0, N),
+ * N = 2^max_depth, read off the cell's octants (bit 0 = x, 1 = y, 2 = z), a face of a cell is emitted iff the cell behind it
+ * is outside [0, N)^3 or not occupied.  Faces are ordered by (cell in extraction order, direction -x +x -y +y -z +z); a face
+ * is four vertex indices, counter-clockwise seen from outside, and the cell's colour word unchanged (R | G<<8 | B<<16 | A<<24).
+ * Vertices are welded: one per lattice corner (ix, iy, iz) in [0, N]^3 that a face uses, ascending in
+ * iz << 2(max_depth+1) | iy << (max_depth+1) | ix.  Position per axis, in binary32, one division, one multiplication and one
+ * addition in this order:   center + (float)(2 i - N) * (edge_length / (float)N)      (edge_length = half edge, as everywhere)
+ * -- NOT the halved-and-summed centres svoslam_extract_voxel_grid computes level by level: a cell's corners are in general
+ * not bit-equal to that call's centre -/+ half a cell.
+ * Blocking.  Outputs are hipMalloc'ed and owned by the caller (svoslam_free): 3 floats per vertex, 4 indices per face, one colour
+ * per face; all NULL and *stats all 0 for an empty surface.  A pool with pending asynchronous fusions is handled as by
+ * svoslam_extract_voxel_grid (the stream is drained first; pool->size == 0, an uninitialised pool, returns the empty surface
+ * before that: an initialised pool holds at least its 8 root children, also while its size lags).  Errors: that call's argument and depth errors;
+ * SVOSLAM_ERR_POOL_LIMIT when 4 x faces exceeds 2^31 - 1.  On any error nothing is left allocated. */
+typedef struct { int32_t cells, faces, vertices; } svoslam_surface_stats;
+int svoslam_extract_surface_mesh(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const float center[3],
+                                 float edge_length, float **d_vertices, uint32_t **d_quads, uint32_t **d_face_colors,
+                                 svoslam_surface_stats *stats, void *stream);
+/* Host only, needs no device: writes a mesh (host arrays) as binary little-endian PLY 1.0 -- vertex x y z float; face = a
+ * uchar-counted list of uint vertex indices, then uchar red green blue alpha.  triangulate != 0 writes two triangles
+ * (0,1,2), (0,2,3) per quad, both with the quad's colour.  SVOSLAM_ERR_INVALID_ARG for an index >= n_vertices (nothing is
+ * written), SVOSLAM_ERR_IO when the file cannot be written (a partial file is removed). */
+int svoslam_mesh_write_ply(const char *path, const float *h_vertices, int32_t n_vertices, const uint32_t *h_quads,
+                           const uint32_t *h_face_colors, int32_t n_faces, int32_t triangulate);
 /* device allocation / copies for callers that do not link the HIP runtime themselves (blocking copies) */
 int svoslam_malloc(void **d_ptr, size_t bytes);
 int svoslam_memcpy_h2d(void *d_dst, const void *h_src, size_t bytes);
@@ -490,7 +518,10 @@ int svoslam_cone_trace_timing_read(float *h_ms_sum, int32_t *h_launches);
 #define SVOSLAM_STAGE_MESH_RASTER 6  /* meshToVoxelGrid: scan-line counts + scans + fragment emission (incl. the two count readbacks) */
 #define SVOSLAM_STAGE_MESH_SORT 7    /* meshToVoxelGrid: sort of the (cell, triangle) fragments */
 #define SVOSLAM_STAGE_MESH_EMIT 8    /* meshToVoxelGrid: last fragment per cell -> voxel centres + colours (incl. the count readback) */
-#define SVOSLAM_STAGE_COUNT 9
+#define SVOSLAM_STAGE_SURFACE_BFS 9    /* extract_surface_mesh: the occupied cells (incl. one readback per level) */
+#define SVOSLAM_STAGE_SURFACE_FACES 10 /* extract_surface_mesh: face masks + scan (incl. the count readback) | emission: two brackets per call, the host's allocations between them are outside */
+#define SVOSLAM_STAGE_SURFACE_WELD 11  /* extract_surface_mesh: corner sort + run heads + scan (incl. the count readback) | scatter: two brackets per call likewise */
+#define SVOSLAM_STAGE_COUNT 12
 int svoslam_stage_timing(uint32_t mask);
 int svoslam_stage_timing_read(int32_t stage, float *h_ms_sum, int32_t *h_pairs);
 

@@ -65,6 +65,10 @@ class CompactStats(C.Structure):
                 ("levels", C.c_int32), ("tiles_dropped", C.c_int32)]
 
 
+class SurfaceStats(C.Structure):
+    _fields_ = [("cells", C.c_int32), ("faces", C.c_int32), ("vertices", C.c_int32)]
+
+
 _lib = None
 _vp, _i32, _f32 = C.c_void_p, C.c_int32, C.c_float
 _fp = C.POINTER(C.c_float)
@@ -173,6 +177,9 @@ SIGNATURES = {
     "svoslam_scene_voxel_grid": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), _fp]),
     "svoslam_scene_svo": (C.c_int, [_vp, C.POINTER(_vp), _fp, _fp, C.POINTER(_i32), C.POINTER(_i32)]),
     "svoslam_free": (C.c_int, [_vp]),
+    "svoslam_extract_surface_mesh": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, _fp, _f32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
+                                                C.POINTER(SurfaceStats), _vp]),
+    "svoslam_mesh_write_ply": (C.c_int, [C.c_char_p, _fp, _i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _i32, _i32]),
     "svoslam_malloc": (C.c_int, [C.POINTER(_vp), C.c_size_t]),
     "svoslam_cone_trace_svo": (C.c_int, [_vp, _i32, _i32, _f32, _fp, _vp, _fp, _f32, _i32, _vp, _vp]),
     "svoslam_cone_trace_svo_band": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _f32, _fp, _vp, _fp, _f32, _i32, _vp, _vp]),
@@ -621,6 +628,36 @@ def extract_voxel_grid(ws, pool, max_depth, center, edge_length):
     return ce, co
 
 
+def extract_surface_mesh(ws, pool, max_depth, center, edge_length):
+    """svoslam_extract_surface_mesh: the surface of the occupied cells at max_depth as a welded quad mesh ->
+    (vertices[n,3] float32, quads[m,4] uint32, colors[m] uint32 (the cells' colour words), stats dict) as numpy arrays"""
+    pv, pq, pc, st = C.c_void_p(), C.c_void_p(), C.c_void_p(), SurfaceStats()
+    check(lib().svoslam_extract_surface_mesh(ws._h, C.byref(pool._p), max_depth, _fa(center, 3), float(edge_length),
+                                             C.byref(pv), C.byref(pq), C.byref(pc), C.byref(st), _stream()))
+    stats = {n: int(getattr(st, n)) for n, _ in SurfaceStats._fields_}
+    try:
+        vertices = copy_from_device(pv.value, (stats["vertices"], 3), np.float32) if pv.value else np.zeros((0, 3), np.float32)
+        quads = copy_from_device(pq.value, (stats["faces"], 4), np.uint32) if pq.value else np.zeros((0, 4), np.uint32)
+        colors = copy_from_device(pc.value, (stats["faces"],), np.uint32) if pc.value else np.zeros(0, np.uint32)
+    finally:
+        for p in (pv, pq, pc):
+            if p.value:
+                lib().svoslam_free(p)
+    return vertices, quads, colors, stats
+
+
+def write_ply(path, vertices, quads, colors, triangulate=False):
+    """svoslam_mesh_write_ply: binary little-endian PLY of a mesh held in numpy arrays (needs no device)"""
+    v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    q = np.ascontiguousarray(quads, dtype=np.uint32).reshape(-1, 4)
+    c = np.ascontiguousarray(colors, dtype=np.uint32).reshape(-1)
+    if c.shape[0] != q.shape[0]:
+        raise ValueError("one colour per quad: %d colours, %d quads" % (c.shape[0], q.shape[0]))
+    u32p = C.POINTER(C.c_uint32)
+    check(lib().svoslam_mesh_write_ply(os.fsencode(str(path)), v.ctypes.data_as(_fp), v.shape[0], q.ctypes.data_as(u32p),
+                                       c.ctypes.data_as(u32p), q.shape[0], 1 if triangulate else 0))
+
+
 # ----------------------------------------------------------------------------- mesh path
 class Mesh:
     """Host mesh as Scene::loadObjFile builds it (recentred, non-indexed)."""
@@ -974,8 +1011,9 @@ def cone_trace_timing_read():
 
 
 (STAGE_MARCH, STAGE_TRACKER, STAGE_FUSE_SORT, STAGE_FUSE_PLAN, STAGE_FUSE_COMMIT, STAGE_MAPS, STAGE_MESH_RASTER, STAGE_MESH_SORT,
- STAGE_MESH_EMIT) = range(9)   # SVOSLAM_STAGE_*
-STAGE_NAMES = ("march", "tracker", "fuse_sort", "fuse_plan", "fuse_commit", "maps", "mesh_raster", "mesh_sort", "mesh_emit")
+ STAGE_MESH_EMIT, STAGE_SURFACE_BFS, STAGE_SURFACE_FACES, STAGE_SURFACE_WELD) = range(12)   # SVOSLAM_STAGE_*
+STAGE_NAMES = ("march", "tracker", "fuse_sort", "fuse_plan", "fuse_commit", "maps", "mesh_raster", "mesh_sort", "mesh_emit", "surface_bfs",
+               "surface_faces", "surface_weld")
 
 
 def stage_timing(stages):

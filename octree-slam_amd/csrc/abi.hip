@@ -351,6 +351,18 @@ int svoslam_extract_voxel_grid(svoslam_workspace *ws, const svoslam_pool *pool, 
   return extract_voxel_grid(ws, pool, max_depth, center, edge_length, d_centers, d_colors, n_out, S(stream));
 }
 
+int svoslam_extract_surface_mesh(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const float center[3],
+                                 float edge_length, float **d_vertices, uint32_t **d_quads, uint32_t **d_face_colors,
+                                 svoslam_surface_stats *stats, void *stream) {
+  NEED_DEVICE();
+  return extract_surface_mesh(ws, pool, max_depth, center, edge_length, d_vertices, d_quads, d_face_colors, stats, S(stream));
+}
+
+int svoslam_mesh_write_ply(const char *path, const float *h_vertices, int32_t n_vertices, const uint32_t *h_quads,
+                           const uint32_t *h_face_colors, int32_t n_faces, int32_t triangulate) {
+  return mesh_write_ply(path, h_vertices, n_vertices, h_quads, h_face_colors, n_faces, triangulate);
+}
+
 int svoslam_free(void *d_ptr) {
   if (d_ptr) SVO_HIP(hipFree(d_ptr));
   return SVOSLAM_OK;

@@ -20,6 +20,9 @@ enum Stage {
   kStageMeshRaster = SVOSLAM_STAGE_MESH_RASTER,  // mesh.hip: tri_scanline_count + scans + scanline_kernel<false / true>
   kStageMeshSort = SVOSLAM_STAGE_MESH_SORT,      // mesh.hip: radix sort of the fragments
   kStageMeshEmit = SVOSLAM_STAGE_MESH_EMIT,      // mesh.hip: voxel_flag + scan + voxel_emit
+  kStageSurfaceBfs = SVOSLAM_STAGE_SURFACE_BFS,      // svo_surface.hip: the occupied cells (bfs_occupied_keys, incl. one readback per level)
+  kStageSurfaceFaces = SVOSLAM_STAGE_SURFACE_FACES,  // svo_surface.hip: face masks + scan (incl. the count readback) | emission: two brackets per call
+  kStageSurfaceWeld = SVOSLAM_STAGE_SURFACE_WELD,    // svo_surface.hip: corner sort + run heads + scan (incl. the count readback) | scatter: two brackets per call
   kStageCount = SVOSLAM_STAGE_COUNT
 };
 

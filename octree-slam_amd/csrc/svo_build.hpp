@@ -1,4 +1,4 @@
-// svo_build.hpp -- the map: fusion (svo_build.hip), key-range sharded commit (svo_keyrange.hip), extraction (svo_extract.hip), paging
+// svo_build.hpp -- the map: fusion (svo_build.hip), key-range sharded commit (svo_keyrange.hip), extraction (svo_extract.hip, svo_surface.hip), paging
 // (pool_paging.hip), re-indexing (pool_compact.hip), and through pool_state.hpp the pool itself
 #pragma once
 #include "common.hpp"
@@ -45,4 +45,13 @@ int svo_from_voxel_grid(svoslam_workspace *ws, const float *d_centers, const flo
                         hipStream_t stream);
 int extract_voxel_grid(svoslam_workspace *ws, const svoslam_pool *pool, int depth, const float center[3], float edge,
                        float **d_centers, float **d_colors, int32_t *n_out, hipStream_t stream);
+// the occupied cells at `depth` as ascending BFS keys, left in the workspace (svo_extract.hip; blocking)
+int bfs_occupied_keys(svoslam_workspace *ws, const svoslam_pool *pool, int depth, hipStream_t stream, const unsigned long long **keys,
+                      int *num_out);
+// surface mesh and its PLY writer (svo_surface.hip)
+int extract_surface_mesh(svoslam_workspace *ws, const svoslam_pool *pool, int depth, const float center[3], float edge,
+                         float **d_vertices, uint32_t **d_quads, uint32_t **d_face_colors, svoslam_surface_stats *stats,
+                         hipStream_t stream);
+int mesh_write_ply(const char *path, const float *h_vertices, int32_t n_vertices, const uint32_t *h_quads, const uint32_t *h_face_colors,
+                   int32_t n_faces, int32_t triangulate);
 }  // namespace svoslam

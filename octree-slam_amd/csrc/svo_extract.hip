@@ -85,12 +85,11 @@ __global__ __launch_bounds__(256) void voxel_grid_from_keys_kernel(const u32 *__
                           (float)((val >> 16) & 0xFF) / 255.0f, (float)((val >> 24) & 0xFF) / 255.0f);
 }
 
-int extract_voxel_grid(svoslam_workspace *ws, const svoslam_pool *pool, int depth, const float center[3], float edge,
-                       float **d_centers, float **d_colors, int32_t *n_out, hipStream_t stream) {
-  if (!ws || !pool || !d_centers || !d_colors || !n_out) return SVOSLAM_ERR_INVALID_ARG;
-  if (depth < 1 || depth > SVOSLAM_MAX_DEPTH) return SVOSLAM_ERR_DEPTH;
-  *d_centers = nullptr; *d_colors = nullptr; *n_out = 0;
-  if (pool->size == 0) return SVOSLAM_OK;
+// The occupied cells at `depth` as BFS keys (leading 1, then one octant triple per level), ascending: a cell is listed iff every
+// node on its path has alpha > 127 and every node above it has children.  The keys stay in the workspace (*keys: bfs_a or bfs_b)
+// until its next extraction.  Blocking (one 4-byte readback per level).  Shared by the voxel grid and the surface mesh.
+int bfs_occupied_keys(svoslam_workspace *ws, const svoslam_pool *pool, int depth, hipStream_t stream, const u64 **keys, int *num_out) {
+  *keys = nullptr; *num_out = 0;
   if (pool->pending > 0) SVO_HIP(hipStreamSynchronize(stream));  // (size itself is not needed by the BFS)
   SVO_TRY(ws->reserve_small());  // (zeroed when created: any_valid and the plan's arrival ticket start at zero)
   SVO_TRY(ws->bfs_a.reserve(8));
@@ -116,11 +115,24 @@ int extract_voxel_grid(svoslam_workspace *ws, const svoslam_pool *pool, int dept
     svoslam::DeviceBuffer *t = cur; cur = nxt; nxt = t;
     num = (int)next_num;
   }
+  if (num > 0) { *keys = cur->as<u64>(); *num_out = num; }
+  return SVOSLAM_OK;
+}
+
+int extract_voxel_grid(svoslam_workspace *ws, const svoslam_pool *pool, int depth, const float center[3], float edge,
+                       float **d_centers, float **d_colors, int32_t *n_out, hipStream_t stream) {
+  if (!ws || !pool || !d_centers || !d_colors || !n_out) return SVOSLAM_ERR_INVALID_ARG;
+  if (depth < 1 || depth > SVOSLAM_MAX_DEPTH) return SVOSLAM_ERR_DEPTH;
+  *d_centers = nullptr; *d_colors = nullptr; *n_out = 0;
+  if (pool->size == 0) return SVOSLAM_OK;
+  const u64 *keys = nullptr;
+  int num = 0;
+  SVO_TRY(bfs_occupied_keys(ws, pool, depth, stream, &keys, &num));
   if (num <= 0) return SVOSLAM_OK;
   float *ce = nullptr, *co = nullptr;
   SVO_HIP(hipMalloc((void **)&ce, (size_t)num * 16));
   SVO_HIP(hipMalloc((void **)&co, (size_t)num * 16));
-  voxel_grid_from_keys_kernel<<<cdiv(num, 256), 256, 0, stream>>>(pool->d_data, cur->as<u64>(), num, center[0], center[1], center[2], edge,
+  voxel_grid_from_keys_kernel<<<cdiv(num, 256), 256, 0, stream>>>(pool->d_data, keys, num, center[0], center[1], center[2], edge,
                                                                   reinterpret_cast<float4 *>(ce), reinterpret_cast<float4 *>(co));
   SVO_LAUNCH_CHECK();
   SVO_HIP(hipStreamSynchronize(stream));
