@@ -364,6 +364,59 @@ int svoslam_extract_surface_mesh(svoslam_workspace *ws, const svoslam_pool *pool
  * written), SVOSLAM_ERR_IO when the file cannot be written (a partial file is removed). */
 int svoslam_mesh_write_ply(const char *path, const float *h_vertices, int32_t n_vertices, const uint32_t *h_quads,
                            const uint32_t *h_face_colors, int32_t n_faces, int32_t triangulate);
+/* Asking the map (no reference counterpart; specification in DESIGN.md section 13).  Both calls work on any pool, the library's
+ * own or foreign words (svoslam_pool_set_nodes), take n inputs in device memory and write caller-allocated device arrays of n
+ * entries, every output pointer optional (NULL: not written).  Neither allocates or reads anything back; both are asynchronous
+ * on `stream`, except that a pool with pending asynchronous fusions is drained first, as by svoslam_extract_voxel_grid.  A pool
+ * whose deferred commit waits for its apply is seen as a renderer sees it: in its old state.  One ray or point per lane in the
+ * caller's order: coherent neighbours (rays of one view, points of one scan) are faster than shuffled ones.
+ * Errors: SVOSLAM_ERR_INVALID_ARG for n < 0, max_depth outside [1, SVOSLAM_MAX_DEPTH], !(edge_length > 0), NULL center, and with
+ * n > 0 a NULL pool, an uninitialised pool or NULL inputs.  n == 0 is SVOSLAM_OK and launches nothing.
+ *
+ * svoslam_pool_cast_rays: the first occupied cell along each ray, by exact traversal -- no step length, nothing is jumped.
+ *   Occupied set: exactly the cells svoslam_extract_voxel_grid(pool, max_depth) returns and svoslam_extract_surface_mesh wraps
+ *     -- every node on the path at levels 1..d has alpha > 127, every node at levels 1..d-1 has children; a childless node above
+ *     d contributes nothing; a d below the fused depth casts against the mip alpha.
+ *   Geometry: the mesh's lattice, so hits lie on mesh faces.  N = 2^d, h = edge_length / (float)N; plane k (0..N) of axis a is
+ *     P_a(k) = center_a + (float)(2k - N) * h; cell x spans P(x)..P(x+1).  All arithmetic is binary32, every product and sum
+ *     rounded on its own, in the order written.
+ *   Ray: d_rays holds origin o then direction v (6 floats per ray; v need not be a unit vector), a point is o + t v, and
+ *     r_a = 1.0f / v_a once per ray for v_a != 0.  The parameter of a plane is (P_a(k) - o_a) * r_a.
+ *   Cell of a coordinate: c_a(p) = the number of k in 1..N-1 with P_a(k) <= p; with v_a < 0 the comparison is <, so a point on a
+ *     plane belongs to the cell it is moving into.
+ *   Start: with P_a(0) <= o_a <= P_a(N) on all axes the origin is inside: cell (c_x(o_x), c_y(o_y), c_z(o_z)), t = 0, face 6.
+ *     Otherwise per axis with v_a != 0 the near and far root planes are 0 and N (swapped for v_a < 0); t_enter is the largest
+ *     near parameter, the entry axis the lowest that attains it; a miss if t_enter < 0, if t_enter exceeds the smallest far
+ *     parameter, or if an axis with v_a == 0 has o_a outside the root.  The entry axis starts at 0 or N-1, the others at
+ *     c_b(o_b + t_enter * v_b); t = t_enter.
+ *   Step: walk the current cell's path from the root.  The first node with alpha <= 127, or without children above level d, at
+ *     level l frees its aligned block of 2^(d-l) cells per axis [lo, hi]; reaching level d with alpha > 127 is the hit.  From a
+ *     free block: the parameter of the leaving plane (hi+1 for v_a > 0, lo for v_a < 0) of each axis with v_a != 0; the smallest
+ *     wins, the lowest axis on a tie (no parameter below +inf: a miss).  That axis moves to the first cell beyond the block --
+ *     outside [0, N) the ray has left the root: a miss.  Each other coordinate becomes c_b of the point at that parameter,
+ *     clamped to the block's range on b, and never moves backwards against the sign of v_b.  t = max(t, that parameter).  A t
+ *     above t_max is a miss, here and at the start.  At most 3N steps (every coordinate is monotone, one advances strictly).
+ *   d_t_max: n floats, or NULL for unlimited.
+ *   Outputs: d_t the entry parameter of the hit cell (+inf: miss; NaN: invalid ray -- a non-finite component or v == 0 -- which
+ *     does no traversal); d_node the level-d node (-1: no hit); d_cell = x | y << 16 | z << 32 | face << 48, face the direction
+ *     id of the face entered as in svoslam_extract_surface_mesh (-x +x -y +y -z +z = 0..5: v_x > 0 enters through 0), 6 = the
+ *     origin was inside the cell (all ones: no hit); d_color the node's colour word (0: no hit); d_steps the blocks visited,
+ *     the hit block included.
+ *
+ * svoslam_pool_query_points: the node that holds each point (d_points: 3 floats per point), by the FUSION's descent -- octant
+ *   bits from p > c, the edge halved, the centre moved by +-edge (computeKey) -- to max_depth or the first childless node, so a
+ *   point that was fused is found in its own leaf.  A point with !(center_a - edge_length <= p_a <= center_a + edge_length) on
+ *   any axis is outside (a NaN by the same test).  The ray cast is tied to the mesh's planes, the lookup to the fusion's halved-
+ *   and-summed centres: the two boundaries of a cell differ by float rounding only, as the mesh's vertices and the voxel
+ *   grid's centres do.
+ *   Outputs: d_node (-1: outside), d_level (the node's level, 1..max_depth; 0: outside), d_key (a leading 1, then one octant
+ *   triple per level walked: the fusion's key format; 0: outside), d_color (the node's colour word; 0: outside). */
+int svoslam_pool_cast_rays(const svoslam_pool *pool, int32_t max_depth, const float center[3], float edge_length, const float *d_rays,
+                           const float *d_t_max, int32_t n, float *d_t, int32_t *d_node, uint64_t *d_cell, uint32_t *d_color,
+                           uint32_t *d_steps, void *stream);
+int svoslam_pool_query_points(const svoslam_pool *pool, int32_t max_depth, const float center[3], float edge_length,
+                              const float *d_points, int32_t n, int32_t *d_node, int32_t *d_level, uint64_t *d_key, uint32_t *d_color,
+                              void *stream);
 /* device allocation / copies for callers that do not link the HIP runtime themselves (blocking copies) */
 int svoslam_malloc(void **d_ptr, size_t bytes);
 int svoslam_memcpy_h2d(void *d_dst, const void *h_src, size_t bytes);
@@ -521,7 +574,8 @@ int svoslam_cone_trace_timing_read(float *h_ms_sum, int32_t *h_launches);
 #define SVOSLAM_STAGE_SURFACE_BFS 9    /* extract_surface_mesh: the occupied cells (incl. one readback per level) */
 #define SVOSLAM_STAGE_SURFACE_FACES 10 /* extract_surface_mesh: face masks + scan (incl. the count readback) | emission: two brackets per call, the host's allocations between them are outside */
 #define SVOSLAM_STAGE_SURFACE_WELD 11  /* extract_surface_mesh: corner sort + run heads + scan (incl. the count readback) | scatter: two brackets per call likewise */
-#define SVOSLAM_STAGE_COUNT 12
+#define SVOSLAM_STAGE_QUERY 12         /* svoslam_pool_cast_rays / svoslam_pool_query_points: the kernel, one bracket per call */
+#define SVOSLAM_STAGE_COUNT 13
 int svoslam_stage_timing(uint32_t mask);
 int svoslam_stage_timing_read(int32_t stage, float *h_ms_sum, int32_t *h_pairs);
 

@@ -180,6 +180,8 @@ SIGNATURES = {
     "svoslam_extract_surface_mesh": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, _fp, _f32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                                                 C.POINTER(SurfaceStats), _vp]),
     "svoslam_mesh_write_ply": (C.c_int, [C.c_char_p, _fp, _i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _i32, _i32]),
+    "svoslam_pool_cast_rays": (C.c_int, [C.POINTER(_PoolStruct), _i32, _fp, _f32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "svoslam_pool_query_points": (C.c_int, [C.POINTER(_PoolStruct), _i32, _fp, _f32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "svoslam_malloc": (C.c_int, [C.POINTER(_vp), C.c_size_t]),
     "svoslam_cone_trace_svo": (C.c_int, [_vp, _i32, _i32, _f32, _fp, _vp, _fp, _f32, _i32, _vp, _vp]),
     "svoslam_cone_trace_svo_band": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _f32, _fp, _vp, _fp, _f32, _i32, _vp, _vp]),
@@ -658,6 +660,62 @@ def write_ply(path, vertices, quads, colors, triangulate=False):
                                        c.ctypes.data_as(u32p), q.shape[0], 1 if triangulate else 0))
 
 
+def _query(inputs, width, fields, outputs, call):
+    """shared by cast_rays / query_points: numpy or cuda-tensor input [n, width] -> dict of the requested outputs, of the same kind.
+    uint32 / uint64 results are computed in int32 / int64 tensors and viewed as unsigned on the way out (numpy) or left signed
+    bit patterns (torch, which has no arithmetic on unsigned 32 / 64-bit)."""
+    import torch
+    as_torch = isinstance(inputs, torch.Tensor)
+    t_in = inputs if as_torch else torch.from_numpy(np.ascontiguousarray(inputs, dtype=np.float32))
+    if as_torch and not t_in.is_cuda:
+        raise ValueError("a tensor input has to be a cuda tensor (pass numpy arrays for host data)")
+    t_in = t_in.to(device="cuda", dtype=torch.float32).reshape(-1, width).contiguous()
+    n = int(t_in.shape[0])
+    names = tuple(fields) if outputs is None else tuple(outputs)
+    for name in names:
+        if name not in fields:
+            raise KeyError("no output %r (have: %s)" % (name, ", ".join(fields)))
+    bufs = {name: torch.empty(n, dtype=fields[name][0], device="cuda") for name in names}
+    call(t_in, n, [_ptr(bufs.get(name)) for name in fields])
+    if as_torch:
+        return bufs
+    return {name: b.cpu().numpy().view(fields[name][1]) for name, b in bufs.items()}
+
+
+def cast_rays(pool, max_depth, center, edge_length, rays, t_max=None, outputs=None):
+    """svoslam_pool_cast_rays: the first occupied cell at max_depth along each ray (rays[n, 6]: origin, direction; t_max[n] or None).
+    -> {"t": float32, "node": int32, "cell": uint64 (x | y << 16 | z << 32 | face << 48), "color": uint32, "steps": uint32} as numpy
+    arrays, or as torch tensors (cell int64, color / steps int32: the same bits) when `rays` is a cuda tensor, in which case nothing
+    is synchronised.  `outputs`: the subset of those names to compute (the others are passed as NULL)."""
+    import torch
+    fields = {"t": (torch.float32, np.float32), "node": (torch.int32, np.int32), "cell": (torch.int64, np.uint64),
+              "color": (torch.int32, np.uint32), "steps": (torch.int32, np.uint32)}
+    tm = None
+    if t_max is not None:
+        tm = t_max if isinstance(t_max, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t_max, dtype=np.float32))
+        tm = tm.to(device="cuda", dtype=torch.float32).reshape(-1).contiguous()
+
+    def call(t_in, n, ptrs):
+        if tm is not None and int(tm.shape[0]) != n:
+            raise ValueError("one t_max per ray: %d values, %d rays" % (int(tm.shape[0]), n))
+        check(lib().svoslam_pool_cast_rays(C.byref(pool._p), int(max_depth), _fa(center, 3), float(edge_length), _ptr(t_in), _ptr(tm), n,
+                                           *ptrs, _stream()))
+    return _query(rays, 6, fields, outputs, call)
+
+
+def query_points(pool, max_depth, center, edge_length, points, outputs=None):
+    """svoslam_pool_query_points: the node that holds each point (points[n, 3]), by the fusion's own descent to max_depth or the first
+    childless node.  -> {"node": int32 (-1 outside), "level": int32, "key": uint64, "color": uint32}, numpy or torch as cast_rays."""
+    import torch
+    fields = {"node": (torch.int32, np.int32), "level": (torch.int32, np.int32), "key": (torch.int64, np.uint64),
+              "color": (torch.int32, np.uint32)}
+
+    def call(t_in, n, ptrs):
+        check(lib().svoslam_pool_query_points(C.byref(pool._p), int(max_depth), _fa(center, 3), float(edge_length), _ptr(t_in), n, *ptrs,
+                                              _stream()))
+    return _query(points, 3, fields, outputs, call)
+
+
 # ----------------------------------------------------------------------------- mesh path
 class Mesh:
     """Host mesh as Scene::loadObjFile builds it (recentred, non-indexed)."""
@@ -1011,9 +1069,9 @@ def cone_trace_timing_read():
 
 
 (STAGE_MARCH, STAGE_TRACKER, STAGE_FUSE_SORT, STAGE_FUSE_PLAN, STAGE_FUSE_COMMIT, STAGE_MAPS, STAGE_MESH_RASTER, STAGE_MESH_SORT,
- STAGE_MESH_EMIT, STAGE_SURFACE_BFS, STAGE_SURFACE_FACES, STAGE_SURFACE_WELD) = range(12)   # SVOSLAM_STAGE_*
+ STAGE_MESH_EMIT, STAGE_SURFACE_BFS, STAGE_SURFACE_FACES, STAGE_SURFACE_WELD, STAGE_QUERY) = range(13)   # SVOSLAM_STAGE_*
 STAGE_NAMES = ("march", "tracker", "fuse_sort", "fuse_plan", "fuse_commit", "maps", "mesh_raster", "mesh_sort", "mesh_emit", "surface_bfs",
-               "surface_faces", "surface_weld")
+               "surface_faces", "surface_weld", "query")
 
 
 def stage_timing(stages):

@@ -8,6 +8,7 @@
 #include "cone_trace.hpp"
 #include "icp.hpp"
 #include "image_kernels.hpp"
+#include "map_query.hpp"
 #include "mesh.hpp"
 #include "model_depth.hpp"
 #include "frame_io.hpp"
@@ -361,6 +362,20 @@ int svoslam_extract_surface_mesh(svoslam_workspace *ws, const svoslam_pool *pool
 int svoslam_mesh_write_ply(const char *path, const float *h_vertices, int32_t n_vertices, const uint32_t *h_quads,
                            const uint32_t *h_face_colors, int32_t n_faces, int32_t triangulate) {
   return mesh_write_ply(path, h_vertices, n_vertices, h_quads, h_face_colors, n_faces, triangulate);
+}
+
+int svoslam_pool_cast_rays(const svoslam_pool *pool, int32_t max_depth, const float center[3], float edge_length, const float *d_rays,
+                           const float *d_t_max, int32_t n, float *d_t, int32_t *d_node, uint64_t *d_cell, uint32_t *d_color,
+                           uint32_t *d_steps, void *stream) {
+  NEED_DEVICE();
+  return pool_cast_rays(pool, max_depth, center, edge_length, d_rays, d_t_max, n, d_t, d_node, d_cell, d_color, d_steps, S(stream));
+}
+
+int svoslam_pool_query_points(const svoslam_pool *pool, int32_t max_depth, const float center[3], float edge_length,
+                              const float *d_points, int32_t n, int32_t *d_node, int32_t *d_level, uint64_t *d_key, uint32_t *d_color,
+                              void *stream) {
+  NEED_DEVICE();
+  return pool_query_points(pool, max_depth, center, edge_length, d_points, n, d_node, d_level, d_key, d_color, S(stream));
 }
 
 int svoslam_free(void *d_ptr) {
