@@ -757,6 +757,13 @@ int svoslam_camera_set_frame_to_model(svoslam_camera *cam, int32_t enable);
 /* the newest timestamp the camera has accepted (rgbd_camera.cpp:55-59 skips frames that are not newer); *have = 0
  * before the first frame.  Host state, no device access. */
 int svoslam_camera_latest_timestamp(svoslam_camera *cam, int32_t *have, long long *timestamp);
+/* plan of the most recent tracked frame: out[0] form (0 no ICP yet, 1 launch chain, 2 one launch register form
+ * (variant 0), 3 one launch streaming form (variant 1), 4 hybrid: level 2 in the one launch, levels 1..0 by the chain),
+ * out[1] workers, out[2..4] participants[0..2], out[5..7] slots[0..2]; for forms 0 and 1 the last seven are 0, for form 4
+ * the entries of levels 1 and 0 are.  Which form a frame takes follows from image size, svoslam_config.track_mode /
+ * track_stream / track_workers and the CUs the stream may use.  Host state (what svoslam_camera_track enqueued), no device
+ * access; svoslam_camera_reset returns it to form 0.  Frames fed by the stepping API or by apply_delta() do not change it. */
+int svoslam_camera_last_track_plan(const svoslam_camera *cam, int32_t out[8]);
 /* diagnostic (libraries built with -DSVO_TRK_PROF; zeros otherwise): device clock stamps of the last tracked frame's
  * one-launch tracker, h_stamps[32][8] = per ICP iteration {solver: start, fan-in done, rows summed, published;
  * worker 0: start, terms done, row stored, broadcast received}.  Blocking. */

@@ -236,6 +236,7 @@ SIGNATURES = {
     "svoslam_camera_last_vertex": (_vp, [_vp, _i32]),
     "svoslam_camera_last_normal": (_vp, [_vp, _i32]),
     "svoslam_camera_tracking_lost_count": (C.c_int, [_vp, C.POINTER(_i32), _vp]),
+    "svoslam_camera_last_track_plan": (C.c_int, [_vp, C.POINTER(_i32)]),
     "svoslam_camera_latest_timestamp": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(C.c_longlong)]),
     "svoslam_camera_track_profile": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), _vp]),
     "svoslam_timer_start": (C.c_int, [_vp]),
@@ -1266,6 +1267,9 @@ def icp_accumulate(last_v, last_n, cur_v, cur_n, first_pixel, num_pixels, acc):
 
 
 # ----------------------------------------------------------------------------- tracker
+TRACK_FORM_NONE, TRACK_FORM_CHAIN, TRACK_FORM_ONE_LAUNCH, TRACK_FORM_STREAM, TRACK_FORM_HYBRID = range(5)   # Camera.last_track_plan()["form"]
+
+
 class Camera:
     """Mirror of sensor::RGBDCamera (include/octree_slam/sensor/rgbd_camera.h)."""
 
@@ -1371,6 +1375,14 @@ class Camera:
         n = C.c_int32(0)
         check(lib().svoslam_camera_tracking_lost_count(self._h, C.byref(n), _stream()))
         return int(n.value)
+
+    def last_track_plan(self):
+        """svoslam_camera_last_track_plan: what the most recent tracked frame enqueued, as {"form", "workers", "participants" [L0, L1, L2],
+        "slots" [L0, L1, L2]}; form = TRACK_FORM_NONE / _CHAIN / _ONE_LAUNCH / _STREAM / _HYBRID (0..4).  Host state, no device access."""
+        out = (_i32 * 8)()
+        check(lib().svoslam_camera_last_track_plan(self._h, out))
+        v = [int(x) for x in out]
+        return {"form": v[0], "workers": v[1], "participants": v[2:5], "slots": v[5:8]}
 
     def close(self):
         if self._h:

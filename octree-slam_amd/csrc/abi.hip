@@ -640,6 +640,7 @@ int svoslam_camera_tracking_lost_count(svoslam_camera *cam, int32_t *count, void
 int svoslam_camera_latest_timestamp(svoslam_camera *cam, int32_t *have, long long *timestamp) {
   return camera_latest_timestamp(cam, have, timestamp);
 }
+int svoslam_camera_last_track_plan(const svoslam_camera *cam, int32_t out[8]) { return camera_last_track_plan(cam, out); }
 int svoslam_camera_track_profile(svoslam_camera *cam, unsigned long long *h_stamps, void *stream) {
   return camera_track_profile(cam, h_stamps, S(stream));
 }

@@ -548,6 +548,7 @@ struct svoslam_camera {
   unsigned *d_tickets = nullptr;
   hipStream_t cap_stream = nullptr;  // stream whose resident-workgroup capacity is cached below
   int capacity = 0;
+  int last_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // what camera_track last enqueued (svoslam_camera_last_track_plan): form, workers, participants[3], slots[3]
   bool delta_fed = false;  // poses come from camera_apply_delta: there are no maps of the previous frame to track against
   // frame-to-model tracking (off by default): a map set of its own, filled by camera_set_model_depth, that the
   // ICP associates the incoming frame with instead of the previous frame's maps (the TODO of rgbd_camera.cpp:185)
@@ -613,6 +614,7 @@ int camera_reset(svoslam_camera *c) {
   c->ring_slot = 0;
   c->delta_fed = false;
   c->have_model = false;  // (the mode itself is a setting and stays)
+  memset(c->last_plan, 0, sizeof(c->last_plan));
   return SVOSLAM_OK;
 }
 
@@ -772,6 +774,14 @@ static bool track_chain_forced() { return config().track_mode == 1; }
 static bool track_one_launch_forced() { return config().track_mode == 2; }
 static bool track_stream_enabled() { return config().track_stream != 0; }
 
+// the plan of the frame being enqueued, for svoslam_camera_last_track_plan (host state only; form: 1 launch chain, 2 one launch
+// register form, 3 one launch streaming form, 4 hybrid)
+static void record_plan(svoslam_camera *c, int form, const TrackArgs *A) {
+  c->last_plan[0] = form;
+  c->last_plan[1] = A ? A->workers : 0;
+  for (int l = 0; l < 3; l++) { c->last_plan[2 + l] = A ? A->participants[l] : 0; c->last_plan[5 + l] = A ? A->slots[l] : 0; }
+}
+
 // returns 0: the whole frame was enqueued; 1: nothing was (caller: launch chain from level 2); 2 + l: levels 2 .. l + 1 were
 // enqueued in the one launch, the launch chain continues at level l
 static int track_one_launch(svoslam_camera *c, hipStream_t s) {
@@ -803,14 +813,17 @@ static int track_one_launch(svoslam_camera *c, hipStream_t s) {
     if (cap1 >= 2) {
       A.work_v = c->work_v; A.work_n = c->work_n;
       SVO_TRY(track_persistent_plan_stream(A, cap1));
+      record_plan(c, 3, &A);
       return track_persistent_launch(c->d_state, c->d_sync, c->d_tickets, A, s);
     }
   }
   if (A.slots[0] > kTrkSlots && !track_one_launch_forced()) {
     SVO_TRY(track_persistent_plan_coarse(A, c->capacity, 1));
+    record_plan(c, 4, &A);
     SVO_TRY(track_persistent_launch(c->d_state, c->d_sync, c->d_tickets, A, s));
     return 2 + 1;                // the chain continues at level 1
   }
+  record_plan(c, 2, &A);
   return track_persistent_launch(c->d_state, c->d_sync, c->d_tickets, A, s);
 }
 
@@ -831,6 +844,9 @@ int camera_track(svoslam_camera *c, hipStream_t s) {
       return SVOSLAM_OK;
     }
     if (rc >= 2) top_level = rc - 2;  // hybrid: the coarser levels are already enqueued
+    else record_plan(c, 1, nullptr);  // no room for the one launch on this stream's CUs
+  } else if (has_icp) {
+    record_plan(c, 1, nullptr);
   }
   // Work maps: allocated on the first chain-tracked frame (cameras served by the one-launch tracker never pay for them)
   const bool work_maps = true;
@@ -1079,6 +1095,12 @@ int camera_latest_timestamp(svoslam_camera *c, int32_t *have, long long *timesta
   if (!c || !have || !timestamp) return SVOSLAM_ERR_INVALID_ARG;
   *have = c->have_stamp ? 1 : 0;
   *timestamp = c->latest_stamp;
+  return SVOSLAM_OK;
+}
+
+int camera_last_track_plan(const svoslam_camera *c, int32_t out[8]) {
+  if (!c || !out) return SVOSLAM_ERR_INVALID_ARG;
+  for (int i = 0; i < 8; i++) out[i] = c->last_plan[i];
   return SVOSLAM_OK;
 }
 

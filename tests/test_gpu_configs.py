@@ -18,7 +18,7 @@ import os
 import numpy as np
 import pytest
 
-from util import describe_mismatch, same_bits_or_nan
+from util import cfg4_icp_maps, describe_mismatch, q15_bands, same_bits_or_nan
 
 pytestmark = pytest.mark.gpu
 
@@ -85,14 +85,7 @@ def test_cfg4_icp_cost2_load_size_60(env, oracle, w, h):
     """computeICPCost2 at the cfg4 pyramid sizes: load_size = 20*w/640 (60 at 1920, 30, 15; 59 for the ragged one),
     Q15: the d_A array has floor(n/load) entries while ceil(n/load) threads run -- the tail is excluded"""
     pkg, torch, synth, pl = env
-    f = synth.focal_length(1920)
-    d0, _ = synth.render_frame(0, 1920, 1080)
-    d1, _ = synth.render_frame(3, 1920, 1080)
-    step = 1920 // w if w in (960, 480) else 1
-    a0 = np.ascontiguousarray(d0.numpy().view(np.uint16)[::step, ::step][:h, :w])
-    a1 = np.ascontiguousarray(d1.numpy().view(np.uint16)[::step, ::step][:h, :w])
-    v1 = oracle.vertex_map(a0, f, f, 1920, 1080); n1 = oracle.normal_map(v1)
-    v2 = oracle.vertex_map(a1, f, f, 1920, 1080); n2 = oracle.normal_map(v2)
+    v1, n1, v2, n2 = cfg4_icp_maps(oracle, synth, w, h)   # (normals with a live last row: the tail of 1919x1079 could count)
     tens = [torch.from_numpy(x).cuda() for x in (v1, n1, v2, n2)]
     A, b = pkg.icp_cost2(*tens)
     rA, rb = oracle.icp_cost2(v1, n1, v2, n2)
@@ -105,6 +98,11 @@ def test_cfg4_icp_cost2_load_size_60(env, oracle, w, h):
         pkg.icp_accumulate(*tens, first * w, rows * w, acc)
     raw = oracle.icp_cost2_raw(v1, n1, v2, n2)
     assert np.array_equal(acc.cpu().numpy(), raw.astype(np.float64))
+    # pixel bands, one ending inside the Q15 tail (1919x1079: 55 pixels of load 59) and one starting there
+    for first, num in q15_bands(h, w):
+        part = torch.zeros(27, dtype=torch.float64, device="cuda")
+        pkg.icp_accumulate(*tens, first, num, part)
+        assert np.array_equal(part.cpu().numpy(), oracle.icp_cost2_raw(v1, n1, v2, n2, first, num).astype(np.float64)), (first, num)
 
 
 def test_cfg4_tracker_1080p(env, oracle):

@@ -4,7 +4,7 @@ fixed-point ICP sums); float maps are compared bit for bit with NaN == NaN."""
 import numpy as np
 import pytest
 
-from util import describe_mismatch, same_bits_or_nan
+from util import describe_mismatch, icp_cost2_maps, noisy_depth, q15_bands, same_bits_or_nan
 
 pytestmark = pytest.mark.gpu
 
@@ -25,16 +25,6 @@ def u16(t):
 
 def dev16(torch, a):
     return torch.from_numpy(np.ascontiguousarray(a, np.uint16).view(np.int16)).cuda()
-
-
-def noisy_depth(rng, h, w):
-    yy, xx = np.mgrid[0:h, 0:w]
-    d = 1800 + 600 * np.sin(xx / 23.0) * np.cos(yy / 17.0) + rng.normal(scale=3.0, size=(h, w))
-    d[(xx // 40 + yy // 30) % 5 == 0] += 900      # depth discontinuities
-    d = np.clip(d, 0, 65535)
-    d[rng.random((h, w)) < 0.02] = 0              # dropouts
-    d[0:3, 0:5] = 20000                           # > 15000 -> invalid
-    return d.astype(np.uint16)
 
 
 @pytest.mark.parametrize("h,w", [(48, 64), (120, 160), (61, 97), (480, 640)])
@@ -140,27 +130,38 @@ def test_transforms_and_bbox(env, oracle):
     assert (b0 == 0).all() and (b1 == 0).all()
 
 
-@pytest.mark.parametrize("h,w", [(120, 160), (240, 320), (480, 640), (75, 101)])
+# sizes with a Q15 tail: (99, 131) load 4, tail 1; (49, 65) load 2, tail 1; (198, 262) load 8, tail 4; (269, 479) load 14, tail 9
+Q15_TAIL_SIZES = [(99, 131), (49, 65), (198, 262), (269, 479)]
+
+
+@pytest.mark.parametrize("h,w", [(120, 160), (240, 320), (480, 640), (75, 101)] + Q15_TAIL_SIZES)
 def test_icp_cost2(env, oracle, h, w):
+    """computeICPCost2 and its banded building block.  The normal maps have a live last row and column (util.live_last_row), so
+    that at the sizes with a tail the pixels Q15 leaves out would pass the gates if a kernel counted them
+    (test_icp_q15_cpu.py proves that on the oracle alone)"""
     pkg, torch, _ = env
-    rng = np.random.default_rng(w)
-    f = 570.3 * w / 640.0
-    d1 = noisy_depth(rng, h, w)
-    v1 = oracle.vertex_map(d1, f, f, w, h); n1 = oracle.normal_map(v1)
-    T = oracle.icp_update_transform(np.array([0.004, -0.003, 0.002, 0.004, -0.002, 0.003], np.float32))
-    v2 = oracle.transform_vertex_map(v1, T); n2 = oracle.transform_normal_map(n1, T)
-    A, b = pkg.icp_cost2(*(torch.from_numpy(x).cuda() for x in (v1, n1, v2, n2)))
+    v1, n1, v2, n2 = icp_cost2_maps(oracle, h, w)
+    tens = [torch.from_numpy(x).cuda() for x in (v1, n1, v2, n2)]
+    A, b = pkg.icp_cost2(*tens)
     rA, rb = oracle.icp_cost2(v1, n1, v2, n2)
     assert np.array_equal(A, rA) and np.array_equal(b, rb), (A - rA, b - rb)
     assert np.abs(A).max() > 0
     # band partials add up exactly (what the multi-GPU all-reduce relies on)
     acc = torch.zeros(27, dtype=torch.float64, device="cuda")
-    tens = [torch.from_numpy(x).cuda() for x in (v1, n1, v2, n2)]
     rows = [0, h // 3, h // 2 + 1, h]
     for r0, r1 in zip(rows[:-1], rows[1:]):
         pkg.icp_accumulate(*tens, r0 * w, (r1 - r0) * w, acc)
     raw = oracle.icp_cost2_raw(v1, n1, v2, n2)
     assert np.array_equal(acc.cpu().numpy(), raw.astype(np.float64))
+    # pixel bands, one ending inside the tail and one starting there: each band alone, and their sum
+    total = np.zeros(27, np.float64)
+    for first, num in q15_bands(h, w):
+        part = torch.zeros(27, dtype=torch.float64, device="cuda")
+        pkg.icp_accumulate(*tens, first, num, part)
+        want = oracle.icp_cost2_raw(v1, n1, v2, n2, first, num).astype(np.float64)
+        assert np.array_equal(part.cpu().numpy(), want), (first, num)
+        total += want
+    assert np.array_equal(total, raw.astype(np.float64))
 
 
 @pytest.mark.parametrize("h,w", [(120, 160), (480, 640), (75, 101)])
@@ -177,7 +178,7 @@ def test_icp_cost_correspondence_variant(env, oracle, h, w):
     tens = [torch.from_numpy(x).cuda() for x in (v1, n1, v2, n2)]
     A, b, m = pkg.icp_cost(*tens)
     rA, rb, rm = oracle.icp_cost(v1, n1, v2, n2)
-    assert m == rm and m > 100 and m % 10 != 0 or m == rm
+    assert m == rm and m > 100 and m % 10 != 0
     assert np.array_equal(A, rA) and np.array_equal(b, rb), (A - rA, b - rb)
     assert np.abs(A).max() > 0
     A2, b2 = pkg.icp_cost2(*tens)
