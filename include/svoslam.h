@@ -417,6 +417,48 @@ int svoslam_pool_cast_rays(const svoslam_pool *pool, int32_t max_depth, const fl
 int svoslam_pool_query_points(const svoslam_pool *pool, int32_t max_depth, const float center[3], float edge_length,
                               const float *d_points, int32_t n, int32_t *d_node, int32_t *d_level, uint64_t *d_key, uint32_t *d_color,
                               void *stream);
+/* Asking the map by volume (no reference counterpart; specification here and in DESIGN.md section 14).  Both calls follow the
+ * conventions of svoslam_pool_cast_rays above: any pool, n inputs in device memory, caller-allocated device arrays of n entries,
+ * every output pointer optional, nothing allocated or read back, asynchronous on `stream` except that pending asynchronous
+ * fusions are drained first, a pool whose deferred commit waits for its apply seen in its old state, the same argument errors,
+ * n == 0 is SVOSLAM_OK and launches nothing.  One box or point per lane in the caller's order.
+ *   Common: d = max_depth, N = 2^d; the occupied set at d, the planes P_a(k) = center_a + (float)(2k - N) * (edge_length /
+ *     (float)N) and the count c_a(p) = the number of k in 1..N-1 with P_a(k) <= p (strict form: <) are svoslam_pool_cast_rays'.
+ *     The Morton code m of a cell interleaves the bits of x, y, z with x lowest (octant = x | y << 1 | z << 2 per level: the octant
+ *     of level l is bits 3(d-l)..3(d-l)+2 of m).  The block of level l around m is the aligned cube of 2^(d-l) cells per axis:
+ *     the Morton range [m with its low 3(d-l) bits cleared, that + 8^(d-l)).
+ *   The walk over an inclusive cell range [lo, hi] (it defines `steps`): next_in(m) is the smallest Morton code >= m whose cell
+ *     lies in [lo, hi] (pure integer geometry, nothing is loaded).  Start at m = morton(lo).  Repeat: m = next_in(m); stop if
+ *     m > morton(hi); count one step and descend from the root along m's path, l = 1..d: the node is loaded; alpha <= 127, or
+ *     l < d and no children, frees the block of level l: m = the block's end; at l == d the cell is occupied: visit it, m += 1.
+ *     Free space costs one step per block of the tree, as in the ray cast.
+ *
+ * svoslam_pool_count_boxes: the occupied cells in each axis-aligned box (d_boxes: 6 floats per box, min xyz then max xyz).
+ *   Box to cells: a box with a NaN component, with min_a > max_a, or with max_a < P_a(0) or min_a > P_a(N) on any axis is empty:
+ *     count 0, first_cell all ones, first_node -1, steps 0.  Infinities are allowed (-inf..+inf: the whole axis).  Otherwise
+ *     lo_a = c_a(min_a) and hi_a = max(lo_a, strict c_a(max_a)): a box face on a lattice plane does not take in the cell beyond.
+ *   Visit: count += 1; the first visit records first_cell = x | y << 16 | z << 32 and first_node (the level-d node): the lowest
+ *     occupied cell in Morton order.  stop_after > 0 ends the walk as soon as count == stop_after (1: the any-hit collision
+ *     test); <= 0 is unlimited.
+ *   Outputs: d_count, d_first_cell, d_first_node, d_steps (descents).
+ *
+ * svoslam_pool_nearest_occupied: the nearest occupied cell within radius_cells (R, 0..SVOSLAM_MAX_RADIUS_CELLS, else
+ *   SVOSLAM_ERR_INVALID_ARG: 3 R^2 fits an int32) of each point's cell (d_points: 3 floats per point), exactly, in integers.
+ *   A point with a NaN or with !(P_a(0) <= p_a <= P_a(N)) on an axis gives dist2 -2, cell all ones, node -1, colour 0, steps 0.
+ *   Otherwise q_a = c_a(p_a), the range is [max(q - R, 0), min(q + R, N - 1)], best = R^2 + 1, and the walk above runs with one
+ *   more test at each level of the descent, before the load: D = sum_a max(block_lo_a - q_a, 0, q_a - block_hi_a)^2 of the block
+ *   of that level; D >= best skips the block exactly as a free one.  Visit: best = D of the cell = sum (x_a - q_a)^2 (< best by
+ *   the test), and the cell, node and colour word are recorded; the walk ends when best == 0.
+ *   Outputs: d_dist2 the squared centre-to-centre distance in cells to the nearest occupied cell within R, among equally near
+ *     cells the lowest in Morton order (-1: none within R; the distance in metres is sqrt(dist2) * 2 * edge_length / N), d_cell =
+ *     x | y << 16 | z << 32 (all ones: none), d_node (-1: none), d_color (0: none), d_steps descents, however a descent ends. */
+#define SVOSLAM_MAX_RADIUS_CELLS 4096
+int svoslam_pool_count_boxes(const svoslam_pool *pool, int32_t max_depth, const float center[3], float edge_length, const float *d_boxes,
+                             int64_t stop_after, int32_t n, uint64_t *d_count, uint64_t *d_first_cell, int32_t *d_first_node,
+                             uint32_t *d_steps, void *stream);
+int svoslam_pool_nearest_occupied(const svoslam_pool *pool, int32_t max_depth, const float center[3], float edge_length,
+                                  const float *d_points, int32_t radius_cells, int32_t n, int32_t *d_dist2, uint64_t *d_cell,
+                                  int32_t *d_node, uint32_t *d_color, uint32_t *d_steps, void *stream);
 /* device allocation / copies for callers that do not link the HIP runtime themselves (blocking copies) */
 int svoslam_malloc(void **d_ptr, size_t bytes);
 int svoslam_memcpy_h2d(void *d_dst, const void *h_src, size_t bytes);
@@ -574,7 +616,7 @@ int svoslam_cone_trace_timing_read(float *h_ms_sum, int32_t *h_launches);
 #define SVOSLAM_STAGE_SURFACE_BFS 9    /* extract_surface_mesh: the occupied cells (incl. one readback per level) */
 #define SVOSLAM_STAGE_SURFACE_FACES 10 /* extract_surface_mesh: face masks + scan (incl. the count readback) | emission: two brackets per call, the host's allocations between them are outside */
 #define SVOSLAM_STAGE_SURFACE_WELD 11  /* extract_surface_mesh: corner sort + run heads + scan (incl. the count readback) | scatter: two brackets per call likewise */
-#define SVOSLAM_STAGE_QUERY 12         /* svoslam_pool_cast_rays / svoslam_pool_query_points: the kernel, one bracket per call */
+#define SVOSLAM_STAGE_QUERY 12         /* svoslam_pool_cast_rays / _query_points / _count_boxes / _nearest_occupied: the kernel, one bracket per call */
 #define SVOSLAM_STAGE_COUNT 13
 int svoslam_stage_timing(uint32_t mask);
 int svoslam_stage_timing_read(int32_t stage, float *h_ms_sum, int32_t *h_pairs);

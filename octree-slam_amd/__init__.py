@@ -182,6 +182,8 @@ SIGNATURES = {
     "svoslam_mesh_write_ply": (C.c_int, [C.c_char_p, _fp, _i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _i32, _i32]),
     "svoslam_pool_cast_rays": (C.c_int, [C.POINTER(_PoolStruct), _i32, _fp, _f32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "svoslam_pool_query_points": (C.c_int, [C.POINTER(_PoolStruct), _i32, _fp, _f32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "svoslam_pool_count_boxes": (C.c_int, [C.POINTER(_PoolStruct), _i32, _fp, _f32, _vp, C.c_int64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "svoslam_pool_nearest_occupied": (C.c_int, [C.POINTER(_PoolStruct), _i32, _fp, _f32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "svoslam_malloc": (C.c_int, [C.POINTER(_vp), C.c_size_t]),
     "svoslam_cone_trace_svo": (C.c_int, [_vp, _i32, _i32, _f32, _fp, _vp, _fp, _f32, _i32, _vp, _vp]),
     "svoslam_cone_trace_svo_band": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _f32, _fp, _vp, _fp, _f32, _i32, _vp, _vp]),
@@ -662,7 +664,7 @@ def write_ply(path, vertices, quads, colors, triangulate=False):
 
 
 def _query(inputs, width, fields, outputs, call):
-    """shared by cast_rays / query_points: numpy or cuda-tensor input [n, width] -> dict of the requested outputs, of the same kind.
+    """shared by cast_rays / query_points / count_boxes / nearest_occupied: numpy or cuda-tensor input [n, width] -> dict of the requested outputs, of the same kind.
     uint32 / uint64 results are computed in int32 / int64 tensors and viewed as unsigned on the way out (numpy) or left signed
     bit patterns (torch, which has no arithmetic on unsigned 32 / 64-bit)."""
     import torch
@@ -714,6 +716,36 @@ def query_points(pool, max_depth, center, edge_length, points, outputs=None):
     def call(t_in, n, ptrs):
         check(lib().svoslam_pool_query_points(C.byref(pool._p), int(max_depth), _fa(center, 3), float(edge_length), _ptr(t_in), n, *ptrs,
                                               _stream()))
+    return _query(points, 3, fields, outputs, call)
+
+
+def count_boxes(pool, max_depth, center, edge_length, boxes, stop_after=0, outputs=None):
+    """svoslam_pool_count_boxes: the occupied cells at max_depth in each axis-aligned box (boxes[n, 6]: min xyz, max xyz; infinities
+    allowed).  stop_after > 0 ends a box's walk at that count (1: the any-hit collision test).  -> {"count": uint64, "first_cell":
+    uint64 (x | y << 16 | z << 32 of the lowest occupied cell in Morton order; all ones: none), "first_node": int32, "steps": uint32},
+    numpy or torch as cast_rays."""
+    import torch
+    fields = {"count": (torch.int64, np.uint64), "first_cell": (torch.int64, np.uint64), "first_node": (torch.int32, np.int32),
+              "steps": (torch.int32, np.uint32)}
+
+    def call(t_in, n, ptrs):
+        check(lib().svoslam_pool_count_boxes(C.byref(pool._p), int(max_depth), _fa(center, 3), float(edge_length), _ptr(t_in),
+                                             int(stop_after), n, *ptrs, _stream()))
+    return _query(boxes, 6, fields, outputs, call)
+
+
+def nearest_occupied(pool, max_depth, center, edge_length, points, radius_cells, outputs=None):
+    """svoslam_pool_nearest_occupied: the nearest occupied cell at max_depth within radius_cells of each point's cell (points[n, 3]).
+    -> {"dist2": int32 (squared distance in cells; -1: none within the radius, -2: the point is outside the root or NaN; metres =
+    sqrt(dist2) * 2 * edge_length / 2^max_depth), "cell": uint64 (x | y << 16 | z << 32), "node": int32, "color": uint32, "steps":
+    uint32}, numpy or torch as cast_rays."""
+    import torch
+    fields = {"dist2": (torch.int32, np.int32), "cell": (torch.int64, np.uint64), "node": (torch.int32, np.int32),
+              "color": (torch.int32, np.uint32), "steps": (torch.int32, np.uint32)}
+
+    def call(t_in, n, ptrs):
+        check(lib().svoslam_pool_nearest_occupied(C.byref(pool._p), int(max_depth), _fa(center, 3), float(edge_length), _ptr(t_in),
+                                                  int(radius_cells), n, *ptrs, _stream()))
     return _query(points, 3, fields, outputs, call)
 
 

@@ -9,6 +9,7 @@
 #include "icp.hpp"
 #include "image_kernels.hpp"
 #include "map_query.hpp"
+#include "map_volume.hpp"
 #include "mesh.hpp"
 #include "model_depth.hpp"
 #include "frame_io.hpp"
@@ -376,6 +377,22 @@ int svoslam_pool_query_points(const svoslam_pool *pool, int32_t max_depth, const
                               void *stream) {
   NEED_DEVICE();
   return pool_query_points(pool, max_depth, center, edge_length, d_points, n, d_node, d_level, d_key, d_color, S(stream));
+}
+
+int svoslam_pool_count_boxes(const svoslam_pool *pool, int32_t max_depth, const float center[3], float edge_length, const float *d_boxes,
+                             int64_t stop_after, int32_t n, uint64_t *d_count, uint64_t *d_first_cell, int32_t *d_first_node,
+                             uint32_t *d_steps, void *stream) {
+  NEED_DEVICE();
+  return pool_count_boxes(pool, max_depth, center, edge_length, d_boxes, stop_after, n, d_count, d_first_cell, d_first_node, d_steps,
+                          S(stream));
+}
+
+int svoslam_pool_nearest_occupied(const svoslam_pool *pool, int32_t max_depth, const float center[3], float edge_length,
+                                  const float *d_points, int32_t radius_cells, int32_t n, int32_t *d_dist2, uint64_t *d_cell,
+                                  int32_t *d_node, uint32_t *d_color, uint32_t *d_steps, void *stream) {
+  NEED_DEVICE();
+  return pool_nearest_occupied(pool, max_depth, center, edge_length, d_points, radius_cells, n, d_dist2, d_cell, d_node, d_color,
+                               d_steps, S(stream));
 }
 
 int svoslam_free(void *d_ptr) {

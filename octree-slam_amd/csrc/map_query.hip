@@ -20,26 +20,13 @@
 // query_points_kernel 18 VGPRs, 0 bytes of scratch, occupancy 8.
 #include <math.h>
 
+#include "lattice.hpp"
 #include "map_query.hpp"
 #include "stage_timing.hpp"
 
 namespace svoslam {
 
 namespace {
-
-// plane k (0..N) of one axis of the 2^d lattice: the surface mesh's vertex coordinate (svo_surface.hip: weld_scatter_kernel)
-__device__ inline float lattice_plane(float c, int k, int N, float h) { return c + (float)(2 * k - N) * h; }
-
-// lo + the number of k in lo+1 .. lo+size-1 whose plane is <= p (< p when `strict`): the cell of p among the `size` cells (a
-// power of two) that start at lo.  Planes ascend with k, so the count is found by probing; a NaN counts nothing.
-__device__ inline int cell_in_block(float c, int N, float h, float p, int lo, int size, bool strict) {
-  int k = lo;
-  for (int s = size >> 1; s > 0; s >>= 1) {
-    const float pl = lattice_plane(c, k + s, N, h);
-    if (strict ? pl < p : pl <= p) k += s;
-  }
-  return k;
-}
 
 __global__ __launch_bounds__(256) void cast_rays_kernel(const uint32_t *__restrict__ pool, const float *__restrict__ rays,
                                                         const float *__restrict__ t_max, unsigned n, int d, float cx, float cy, float cz,
@@ -205,13 +192,13 @@ __global__ __launch_bounds__(256) void query_points_kernel(const uint32_t *__res
   if (out_color) out_color[i] = color;
 }
 
+}  // namespace
+
 int query_args(const svoslam_pool *pool, int depth, const float center[3], float edge, const void *d_in, int32_t n) {
   if (n < 0 || depth < 1 || depth > SVOSLAM_MAX_DEPTH || !(edge > 0.0f) || !center) return SVOSLAM_ERR_INVALID_ARG;
   if (n > 0 && (!pool || !pool->d_data || !d_in)) return SVOSLAM_ERR_INVALID_ARG;
   return SVOSLAM_OK;
 }
-
-}  // namespace
 
 int pool_cast_rays(const svoslam_pool *pool, int depth, const float center[3], float edge, const float *d_rays, const float *d_t_max,
                    int32_t n, float *d_t, int32_t *d_node, uint64_t *d_cell, uint32_t *d_color, uint32_t *d_steps, hipStream_t stream) {
