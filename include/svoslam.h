@@ -459,6 +459,52 @@ int svoslam_pool_count_boxes(const svoslam_pool *pool, int32_t max_depth, const 
 int svoslam_pool_nearest_occupied(const svoslam_pool *pool, int32_t max_depth, const float center[3], float edge_length,
                                   const float *d_points, int32_t radius_cells, int32_t n, int32_t *d_dist2, uint64_t *d_cell,
                                   int32_t *d_node, uint32_t *d_color, uint32_t *d_steps, void *stream);
+/* The distance field of a map region (no reference counterpart; specification here and in DESIGN.md section 15): for every cell of
+ * a box of cells, the squared distance in cells to the nearest occupied cell if that is within radius_cells, exactly, in integers
+ * -- an Euclidean distance transform truncated at R.  The dense form of svoslam_pool_nearest_occupied: neighbouring cells share
+ * almost all of their answer, so the occupied cells of the region are rasterised once and three separable passes follow.
+ *   Occupied set: d = max_depth (1..SVOSLAM_MAX_DEPTH), N = 2^d; the occupied set at d is svoslam_pool_cast_rays': the cells
+ *     svoslam_extract_voxel_grid(pool, d) lists (below the fused depth the mip alpha decides; a childless node above d
+ *     contributes nothing).  A cell that is not in it is free.
+ *   Region: the cells q with origin_cell_a <= q_a < origin_cell_a + dims_a, in cells at depth d.  It has to lie inside the root:
+ *     0 <= origin_cell_a and origin_cell_a + dims_a <= N.  There is no centre and no edge length: once the occupied set is known
+ *     everything is integers.
+ *   Output: d_dist2, dims[0] * dims[1] * dims[2] values of type int32 in device memory, x fastest: index ((z - oz) * ny + (y - oy)) *
+ *     nx + (x - ox).  With R = radius_cells (0..SVOSLAM_MAX_RADIUS_CELLS) the value at q is the minimum of (cx - qx)^2 + (cy - qy)^2
+ *     + (cz - qz)^2 over ALL occupied cells c of the root -- those outside the region too -- if that minimum is <= R^2, and -1
+ *     otherwise: exactly the dist2 svoslam_pool_nearest_occupied returns for a point inside cell q with the same d and R.  Metres
+ *     are sqrt(dist2) * 2 * edge_length / N.  Only the value is specified, not how it is computed.
+ *   Conventions: those of the calls above.  Any pool (foreign words set with svoslam_pool_set_nodes included); asynchronous on
+ *     `stream`, nothing is read back; pending asynchronous fusions are drained first, as svoslam_extract_voxel_grid drains them;
+ *     a pool whose deferred commit waits for its apply is seen in its old state.  Intermediates (the occupancy of the region
+ *     inflated by R as bit rows, and the field after the x and the y pass) live in grow-only slots of the workspace: a call that
+ *     needs more than the workspace has allocates, a second call of the same size does not.
+ *   Errors: a zero entry of dims is SVOSLAM_OK and launches nothing, if the other arguments are valid.  SVOSLAM_ERR_INVALID_ARG: ws,
+ *     origin_cell or dims NULL; max_depth outside 1..SVOSLAM_MAX_DEPTH; a negative entry of dims; a region not inside the root;
+ *     radius_cells outside 0..SVOSLAM_MAX_RADIUS_CELLS; with a non-empty region a NULL or uninitialised pool or a NULL d_dist2.
+ *     SVOSLAM_ERR_POOL_LIMIT: more than 2^31 - 1 output cells, or an intermediate of more than 2^31 - 1 elements (the inflated region
+ *     at a large R can reach that).  SVOSLAM_ERR_OOM: an allocation failed; nothing the call allocated stays behind on an error.
+ *
+ * svoslam_box_to_cells (host only, needs no device): the inclusive cell range [lo, hi] of an axis-aligned box (min xyz then max xyz)
+ *   at max_depth, by svoslam_pool_count_boxes' "Box to cells" above, the same planes and counts in the same binary32 operations:
+ *   lo_a = c_a(min_a), hi_a = max(lo_a, strict c_a(max_a)); *empty = 1 for a box with a NaN component, with min_a > max_a, or with
+ *   max_a < P_a(0) or min_a > P_a(N) on any axis (lo and hi are still written), else 0.  The values lie in [0, N): the field of the
+ *   box one would hand to svoslam_pool_count_boxes is origin_cell = lo, dims = hi - lo + 1.  SVOSLAM_ERR_INVALID_ARG: a NULL
+ *   pointer, max_depth outside 1..SVOSLAM_MAX_DEPTH, !(edge_length > 0). */
+int svoslam_pool_distance_field(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                                const int32_t dims[3], int32_t radius_cells, int32_t *d_dist2, void *stream);
+int svoslam_box_to_cells(int32_t max_depth, const float center[3], float edge_length, const float box[6], int32_t lo[3], int32_t hi[3],
+                         int32_t *empty);
+/* profiling form of svoslam_pool_distance_field: the same call and the same result, but BLOCKING, with an event before the first
+ * launch and after each of the four: launch_ms = the milliseconds of the raster, the x pass, the y pass and the z pass (zeros when
+ * nothing is launched; NULL: SVOSLAM_ERR_INVALID_ARG).  For tools/map_field_bench.py; each event costs its stream a few
+ * microseconds. */
+int svoslam_pool_distance_field_profile(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                                        const int32_t dims[3], int32_t radius_cells, int32_t *d_dist2, float launch_ms[4], void *stream);
+/* diagnostics: the device pointers and sizes in bytes of the workspace's three distance-field slots (the bit rows, the field after
+ * the x pass, after the y pass; NULL / 0 before the first call): what a test of "a second call of the same size does not allocate"
+ * looks at.  Host only. */
+int svoslam_workspace_field_buffers(const svoslam_workspace *ws, void *d_ptrs[3], uint64_t bytes[3]);
 /* device allocation / copies for callers that do not link the HIP runtime themselves (blocking copies) */
 int svoslam_malloc(void **d_ptr, size_t bytes);
 int svoslam_memcpy_h2d(void *d_dst, const void *h_src, size_t bytes);
@@ -616,7 +662,7 @@ int svoslam_cone_trace_timing_read(float *h_ms_sum, int32_t *h_launches);
 #define SVOSLAM_STAGE_SURFACE_BFS 9    /* extract_surface_mesh: the occupied cells (incl. one readback per level) */
 #define SVOSLAM_STAGE_SURFACE_FACES 10 /* extract_surface_mesh: face masks + scan (incl. the count readback) | emission: two brackets per call, the host's allocations between them are outside */
 #define SVOSLAM_STAGE_SURFACE_WELD 11  /* extract_surface_mesh: corner sort + run heads + scan (incl. the count readback) | scatter: two brackets per call likewise */
-#define SVOSLAM_STAGE_QUERY 12         /* svoslam_pool_cast_rays / _query_points / _count_boxes / _nearest_occupied: the kernel, one bracket per call */
+#define SVOSLAM_STAGE_QUERY 12         /* svoslam_pool_cast_rays / _query_points / _count_boxes / _nearest_occupied: the kernel, one bracket per call; svoslam_pool_distance_field: its four launches, one bracket per call */
 #define SVOSLAM_STAGE_COUNT 13
 int svoslam_stage_timing(uint32_t mask);
 int svoslam_stage_timing_read(int32_t stage, float *h_ms_sum, int32_t *h_pairs);

@@ -184,6 +184,10 @@ SIGNATURES = {
     "svoslam_pool_query_points": (C.c_int, [C.POINTER(_PoolStruct), _i32, _fp, _f32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "svoslam_pool_count_boxes": (C.c_int, [C.POINTER(_PoolStruct), _i32, _fp, _f32, _vp, C.c_int64, _i32, _vp, _vp, _vp, _vp, _vp]),
     "svoslam_pool_nearest_occupied": (C.c_int, [C.POINTER(_PoolStruct), _i32, _fp, _f32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "svoslam_pool_distance_field": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _vp, _vp]),
+    "svoslam_pool_distance_field_profile": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _vp, _fp, _vp]),
+    "svoslam_box_to_cells": (C.c_int, [_i32, _fp, _f32, _fp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "svoslam_workspace_field_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
     "svoslam_malloc": (C.c_int, [C.POINTER(_vp), C.c_size_t]),
     "svoslam_cone_trace_svo": (C.c_int, [_vp, _i32, _i32, _f32, _fp, _vp, _fp, _f32, _i32, _vp, _vp]),
     "svoslam_cone_trace_svo_band": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _f32, _fp, _vp, _fp, _f32, _i32, _vp, _vp]),
@@ -347,6 +351,12 @@ class Workspace:
         if self._h:
             lib().svoslam_workspace_destroy(self._h)
             self._h = C.c_void_p()
+
+    def field_buffers(self):
+        """svoslam_workspace_field_buffers: [(device pointer, bytes)] of the three distance-field slots (diagnostics)"""
+        ptrs, sizes = (_vp * 3)(), (C.c_uint64 * 3)()
+        check(lib().svoslam_workspace_field_buffers(self._h, ptrs, sizes))
+        return [(int(ptrs[k] or 0), int(sizes[k])) for k in range(3)]
 
     def __del__(self):
         try:
@@ -747,6 +757,39 @@ def nearest_occupied(pool, max_depth, center, edge_length, points, radius_cells,
         check(lib().svoslam_pool_nearest_occupied(C.byref(pool._p), int(max_depth), _fa(center, 3), float(edge_length), _ptr(t_in),
                                                   int(radius_cells), n, *ptrs, _stream()))
     return _query(points, 3, fields, outputs, call)
+
+
+def distance_field(ws, pool, max_depth, origin, dims, radius_cells, as_tensor=False, launch_ms=None):
+    """svoslam_pool_distance_field: for every cell of the region origin[3] .. origin + dims[3] (cells at max_depth, x y z) the squared
+    distance in cells to the nearest occupied cell of the map within radius_cells, -1 where there is none: an exact Euclidean
+    distance transform truncated at the radius.  -> int32 [nz, ny, nx] (metres = sqrt(dist2) * 2 * edge_length / 2^max_depth), a
+    numpy array, or with as_tensor a cuda tensor, in which case nothing is synchronised.  `launch_ms`: a list that receives the
+    milliseconds of the four launches (raster, x, y, z pass): svoslam_pool_distance_field_profile, which blocks."""
+    import torch
+    o, n = [int(v) for v in origin], [int(v) for v in dims]
+    if len(o) != 3 or len(n) != 3:
+        raise ValueError("origin and dims are three cells each (x, y, z)")
+    out = torch.empty([max(v, 0) for v in reversed(n)], dtype=torch.int32, device="cuda")
+    if launch_ms is None:
+        check(lib().svoslam_pool_distance_field(ws._h, C.byref(pool._p), int(max_depth), (_i32 * 3)(*o), (_i32 * 3)(*n), int(radius_cells),
+                                                _ptr(out), _stream()))
+    else:
+        ms = (C.c_float * 4)()
+        check(lib().svoslam_pool_distance_field_profile(ws._h, C.byref(pool._p), int(max_depth), (_i32 * 3)(*o), (_i32 * 3)(*n),
+                                                        int(radius_cells), _ptr(out), ms, _stream()))
+        launch_ms[:] = [float(v) for v in ms]
+    return out if as_tensor else out.cpu().numpy()
+
+
+def box_to_cells(max_depth, center, edge_length, box):
+    """svoslam_box_to_cells (host only): the inclusive cell range (lo[3], hi[3]) at max_depth of the axis-aligned box[6] (min xyz, max
+    xyz; infinities allowed) exactly as count_boxes takes it, or None for an empty box (a NaN, min > max, outside the root).  The
+    field of that box: distance_field(ws, pool, max_depth, lo, hi - lo + 1, radius_cells)."""
+    lo, hi, empty = (_i32 * 3)(), (_i32 * 3)(), _i32(0)
+    check(lib().svoslam_box_to_cells(int(max_depth), _fa(center, 3), float(edge_length), _fa(box, 6), lo, hi, C.byref(empty)))
+    if empty.value:
+        return None
+    return np.array(lo[:], np.int32), np.array(hi[:], np.int32)
 
 
 # ----------------------------------------------------------------------------- mesh path

@@ -8,6 +8,7 @@
 #include "cone_trace.hpp"
 #include "icp.hpp"
 #include "image_kernels.hpp"
+#include "map_field.hpp"
 #include "map_query.hpp"
 #include "map_volume.hpp"
 #include "mesh.hpp"
@@ -393,6 +394,31 @@ int svoslam_pool_nearest_occupied(const svoslam_pool *pool, int32_t max_depth, c
   NEED_DEVICE();
   return pool_nearest_occupied(pool, max_depth, center, edge_length, d_points, radius_cells, n, d_dist2, d_cell, d_node, d_color,
                                d_steps, S(stream));
+}
+
+int svoslam_pool_distance_field(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                                const int32_t dims[3], int32_t radius_cells, int32_t *d_dist2, void *stream) {
+  NEED_DEVICE();
+  return pool_distance_field(ws, pool, max_depth, origin_cell, dims, radius_cells, d_dist2, nullptr, S(stream));
+}
+
+int svoslam_pool_distance_field_profile(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                                        const int32_t dims[3], int32_t radius_cells, int32_t *d_dist2, float launch_ms[4], void *stream) {
+  NEED_DEVICE();
+  if (!launch_ms) return SVOSLAM_ERR_INVALID_ARG;
+  return pool_distance_field(ws, pool, max_depth, origin_cell, dims, radius_cells, d_dist2, launch_ms, S(stream));
+}
+
+int svoslam_box_to_cells(int32_t max_depth, const float center[3], float edge_length, const float box[6], int32_t lo[3], int32_t hi[3],
+                         int32_t *empty) {
+  return box_to_cells(max_depth, center, edge_length, box, lo, hi, empty);
+}
+
+int svoslam_workspace_field_buffers(const svoslam_workspace *ws, void *d_ptrs[3], uint64_t bytes[3]) {
+  if (!ws || !d_ptrs || !bytes) return SVOSLAM_ERR_INVALID_ARG;
+  const svoslam::DeviceBuffer *slots[3] = {&ws->field_bits, &ws->field_a, &ws->field_b};
+  for (int k = 0; k < 3; k++) { d_ptrs[k] = slots[k]->ptr; bytes[k] = slots[k]->bytes; }
+  return SVOSLAM_OK;
 }
 
 int svoslam_free(void *d_ptr) {
