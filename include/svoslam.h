@@ -505,6 +505,45 @@ int svoslam_pool_distance_field_profile(svoslam_workspace *ws, const svoslam_poo
  * the x pass, after the y pass; NULL / 0 before the first call): what a test of "a second call of the same size does not allocate"
  * looks at.  Host only. */
 int svoslam_workspace_field_buffers(const svoslam_workspace *ws, void *d_ptrs[3], uint64_t bytes[3]);
+/* The reach field of a map region (no reference counterpart; specification here and in DESIGN.md section 16): for every cell of a
+ * box of cells, the number of face-neighbour moves of the shortest path from any seed cell that stays in traversable cells of the
+ * region -- a cost-to-go field (navigation function, wavefront).  Exact, in integers.
+ *   d, N, the occupied set and the region are exactly those of svoslam_pool_distance_field: cells at depth d = max_depth, the
+ *     region origin_cell .. origin_cell + dims inside the root.
+ *   Traversable set T: with r = clearance_cells (0..SVOSLAM_MAX_RADIUS_CELLS) a region cell q is traversable iff no occupied cell
+ *     of the WHOLE root lies within squared distance r^2 of it -- exactly the condition under which svoslam_pool_distance_field
+ *     with radius_cells = r writes -1 at q.  Occupied cells up to r outside the region block cells inside it; at r = 0 an occupied
+ *     cell itself is blocked.
+ *   Seeds: d_seeds, n_seeds triples (x, y, z) of int32 absolute cells at depth d, in device memory.  A seed counts if it lies in
+ *     the region and is in T; any other seed is ignored (negative or >= N included).  Duplicates are allowed.  n_seeds = 0 is
+ *     allowed, and d_seeds may then be NULL.
+ *   Output: d_steps, dims[0] * dims[1] * dims[2] values of type int32 in device memory, x fastest, indexed as d_dist2 is.  The
+ *     value at q is -2 if q is not in T; otherwise the number of moves of the shortest path from any counted seed to q, where a
+ *     move goes to one of the six face neighbours and every cell of the path is in T and IN THE REGION (0 at a counted seed); -1
+ *     if there is no such path.  Metres along the path = steps * 2 * edge_length / N.  Only these values are specified, not how
+ *     they are computed.  stats (may be NULL): seeds_used = the seed entries that counted, duplicates counted each; rounds and
+ *     tile_runs are diagnostics with no specified value (the launches of the relaxation and the tiles they worked on).
+ *   Conventions: those of svoslam_pool_distance_field -- any pool; pending asynchronous fusions are drained first; a deferred
+ *     commit's pool is read in its old state; the intermediates (the distance field's, the traversable bit rows and the tile flags)
+ *     live in grow-only slots of the workspace, so a second call of the same size allocates nothing -- with ONE DIFFERENCE: THE CALL
+ *     BLOCKS.  The relaxation runs in rounds and the host reads one small convergence record (32 bytes) per round, as
+ *     svoslam_extract_surface_mesh reads back once per level; after the last round's readback the finishing launch is
+ *     asynchronous on `stream`, like the output of every other call.  The result does not depend on scheduling.
+ *   Errors: a zero entry of dims is SVOSLAM_OK and launches nothing, if the other arguments are valid.  SVOSLAM_ERR_INVALID_ARG:
+ *     those of svoslam_pool_distance_field (clearance_cells for radius_cells, d_steps for d_dist2), n_seeds < 0, NULL d_seeds with
+ *     n_seeds > 0.  SVOSLAM_ERR_POOL_LIMIT: the limits of svoslam_pool_distance_field with radius_cells = clearance_cells, or more than
+ *     2^24 - 1 tiles of 64 x 8 x 8 cells (a region one cell wide in x with ny * nz near 2^31), decided before anything is allocated
+ *     or written.  SVOSLAM_ERR_OOM: an allocation failed; the slots the call grew are released.
+ *     SVOSLAM_ERR_HIP with a text in svoslam_last_error: the round cap (tiles * cells per tile + 1) was reached, which the
+ *     argument of section 16 rules out. */
+typedef struct { int32_t rounds, tile_runs, seeds_used; } svoslam_reach_stats;
+int svoslam_pool_reach_field(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                             const int32_t dims[3], int32_t clearance_cells, const int32_t *d_seeds, int32_t n_seeds, int32_t *d_steps,
+                             svoslam_reach_stats *stats /* may be NULL */, void *stream);
+/* diagnostics: the device pointers and sizes in bytes of the workspace's two reach-field slots (the traversable bit rows; the
+ * control record with the tile flags; NULL / 0 before the first call), as svoslam_workspace_field_buffers shows the distance
+ * field's.  Host only. */
+int svoslam_workspace_reach_buffers(const svoslam_workspace *ws, void *d_ptrs[2], uint64_t bytes[2]);
 /* device allocation / copies for callers that do not link the HIP runtime themselves (blocking copies) */
 int svoslam_malloc(void **d_ptr, size_t bytes);
 int svoslam_memcpy_h2d(void *d_dst, const void *h_src, size_t bytes);
@@ -662,7 +701,7 @@ int svoslam_cone_trace_timing_read(float *h_ms_sum, int32_t *h_launches);
 #define SVOSLAM_STAGE_SURFACE_BFS 9    /* extract_surface_mesh: the occupied cells (incl. one readback per level) */
 #define SVOSLAM_STAGE_SURFACE_FACES 10 /* extract_surface_mesh: face masks + scan (incl. the count readback) | emission: two brackets per call, the host's allocations between them are outside */
 #define SVOSLAM_STAGE_SURFACE_WELD 11  /* extract_surface_mesh: corner sort + run heads + scan (incl. the count readback) | scatter: two brackets per call likewise */
-#define SVOSLAM_STAGE_QUERY 12         /* svoslam_pool_cast_rays / _query_points / _count_boxes / _nearest_occupied: the kernel, one bracket per call; svoslam_pool_distance_field: its four launches, one bracket per call */
+#define SVOSLAM_STAGE_QUERY 12         /* svoslam_pool_cast_rays / _query_points / _count_boxes / _nearest_occupied: the kernel, one bracket per call; svoslam_pool_distance_field: its four launches, one bracket per call; svoslam_pool_reach_field: the field's launches and every launch and readback of the relaxation, one bracket per call */
 #define SVOSLAM_STAGE_COUNT 13
 int svoslam_stage_timing(uint32_t mask);
 int svoslam_stage_timing_read(int32_t stage, float *h_ms_sum, int32_t *h_pairs);

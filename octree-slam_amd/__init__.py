@@ -46,6 +46,10 @@ class _PoolStruct(C.Structure):
                 ("pending", C.c_int32), ("pending_bound", C.c_int64), ("tracker", C.c_void_p)]
 
 
+class _ReachStats(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("tile_runs", C.c_int32), ("seeds_used", C.c_int32)]
+
+
 class MeshStruct(C.Structure):
     _fields_ = [("vbo", C.POINTER(C.c_float)), ("tbo", C.POINTER(C.c_float)), ("n_tris", C.c_int32), ("tbosize", C.c_int32),
                 ("bbox0", C.c_float * 3), ("bbox1", C.c_float * 3)]
@@ -188,6 +192,9 @@ SIGNATURES = {
     "svoslam_pool_distance_field_profile": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _vp, _fp, _vp]),
     "svoslam_box_to_cells": (C.c_int, [_i32, _fp, _f32, _fp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
     "svoslam_workspace_field_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "svoslam_pool_reach_field": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _vp, _i32, _vp,
+                                           C.POINTER(_ReachStats), _vp]),
+    "svoslam_workspace_reach_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
     "svoslam_malloc": (C.c_int, [C.POINTER(_vp), C.c_size_t]),
     "svoslam_cone_trace_svo": (C.c_int, [_vp, _i32, _i32, _f32, _fp, _vp, _fp, _f32, _i32, _vp, _vp]),
     "svoslam_cone_trace_svo_band": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _f32, _fp, _vp, _fp, _f32, _i32, _vp, _vp]),
@@ -357,6 +364,12 @@ class Workspace:
         ptrs, sizes = (_vp * 3)(), (C.c_uint64 * 3)()
         check(lib().svoslam_workspace_field_buffers(self._h, ptrs, sizes))
         return [(int(ptrs[k] or 0), int(sizes[k])) for k in range(3)]
+
+    def reach_buffers(self):
+        """svoslam_workspace_reach_buffers: [(device pointer, bytes)] of the two reach-field slots (diagnostics)"""
+        ptrs, sizes = (_vp * 2)(), (C.c_uint64 * 2)()
+        check(lib().svoslam_workspace_reach_buffers(self._h, ptrs, sizes))
+        return [(int(ptrs[k] or 0), int(sizes[k])) for k in range(2)]
 
     def __del__(self):
         try:
@@ -778,6 +791,33 @@ def distance_field(ws, pool, max_depth, origin, dims, radius_cells, as_tensor=Fa
         check(lib().svoslam_pool_distance_field_profile(ws._h, C.byref(pool._p), int(max_depth), (_i32 * 3)(*o), (_i32 * 3)(*n),
                                                         int(radius_cells), _ptr(out), ms, _stream()))
         launch_ms[:] = [float(v) for v in ms]
+    return out if as_tensor else out.cpu().numpy()
+
+
+def reach_field(ws, pool, max_depth, origin, dims, clearance_cells, seeds, as_tensor=False, stats=None):
+    """svoslam_pool_reach_field: for every cell of the region origin[3] .. origin + dims[3] (cells at max_depth, x y z) the number of
+    face-neighbour moves of the shortest path from any of `seeds` ([n, 3] absolute cells: an array, or an int32 cuda tensor) that
+    stays in the region and in cells with no occupied cell within clearance_cells (those where distance_field with that radius is
+    -1); 0 at a seed that counts, -1 where no path leads, -2 where the cell is blocked.  -> int32 [nz, ny, nx] (metres along the
+    path = steps * 2 * edge_length / 2^max_depth), a numpy array, or with as_tensor a cuda tensor.  The call blocks either way:
+    the host reads a convergence record per round.  `stats`: a dict that receives rounds, tile_runs and seeds_used."""
+    import torch
+    o, n = [int(v) for v in origin], [int(v) for v in dims]
+    if len(o) != 3 or len(n) != 3:
+        raise ValueError("origin and dims are three cells each (x, y, z)")
+    if isinstance(seeds, torch.Tensor):
+        if not seeds.is_cuda or seeds.dtype != torch.int32:
+            raise ValueError("a seeds tensor is int32 on the device")
+        t_seeds = seeds.reshape(-1, 3).contiguous()
+    else:
+        t_seeds = torch.from_numpy(np.ascontiguousarray(np.asarray(seeds, np.int32).reshape(-1, 3))).cuda()
+    count = int(t_seeds.shape[0])
+    out = torch.empty([max(v, 0) for v in reversed(n)], dtype=torch.int32, device="cuda")
+    st = _ReachStats()
+    check(lib().svoslam_pool_reach_field(ws._h, C.byref(pool._p), int(max_depth), (_i32 * 3)(*o), (_i32 * 3)(*n), int(clearance_cells),
+                                         _ptr(t_seeds) if count else None, count, _ptr(out), C.byref(st), _stream()))
+    if stats is not None:
+        stats.update(rounds=int(st.rounds), tile_runs=int(st.tile_runs), seeds_used=int(st.seeds_used))
     return out if as_tensor else out.cpu().numpy()
 
 

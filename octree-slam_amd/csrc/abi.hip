@@ -10,6 +10,7 @@
 #include "image_kernels.hpp"
 #include "map_field.hpp"
 #include "map_query.hpp"
+#include "map_reach.hpp"
 #include "map_volume.hpp"
 #include "mesh.hpp"
 #include "model_depth.hpp"
@@ -407,6 +408,20 @@ int svoslam_pool_distance_field_profile(svoslam_workspace *ws, const svoslam_poo
   NEED_DEVICE();
   if (!launch_ms) return SVOSLAM_ERR_INVALID_ARG;
   return pool_distance_field(ws, pool, max_depth, origin_cell, dims, radius_cells, d_dist2, launch_ms, S(stream));
+}
+
+int svoslam_pool_reach_field(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                             const int32_t dims[3], int32_t clearance_cells, const int32_t *d_seeds, int32_t n_seeds, int32_t *d_steps,
+                             svoslam_reach_stats *stats, void *stream) {
+  NEED_DEVICE();
+  return pool_reach_field(ws, pool, max_depth, origin_cell, dims, clearance_cells, d_seeds, n_seeds, d_steps, stats, S(stream));
+}
+
+int svoslam_workspace_reach_buffers(const svoslam_workspace *ws, void *d_ptrs[2], uint64_t bytes[2]) {
+  if (!ws || !d_ptrs || !bytes) return SVOSLAM_ERR_INVALID_ARG;
+  const svoslam::DeviceBuffer *slots[2] = {&ws->reach_bits, &ws->reach_flags};
+  for (int k = 0; k < 2; k++) { d_ptrs[k] = slots[k]->ptr; bytes[k] = slots[k]->bytes; }
+  return SVOSLAM_OK;
 }
 
 int svoslam_box_to_cells(int32_t max_depth, const float center[3], float edge_length, const float box[6], int32_t lo[3], int32_t hi[3],

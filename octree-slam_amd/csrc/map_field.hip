@@ -154,7 +154,7 @@ struct LaunchEvents {
 }  // namespace
 
 int pool_distance_field(svoslam_workspace *ws, const svoslam_pool *pool, int depth, const int32_t origin[3], const int32_t dims[3],
-                        int32_t R, int32_t *d_dist2, float *launch_ms, hipStream_t stream) {
+                        int32_t R, int32_t *d_dist2, float *launch_ms, hipStream_t stream, long long *outer_bracket) {
   if (launch_ms) launch_ms[0] = launch_ms[1] = launch_ms[2] = launch_ms[3] = 0.0f;
   if (!ws || !origin || !dims || depth < 1 || depth > SVOSLAM_MAX_DEPTH) return SVOSLAM_ERR_INVALID_ARG;
   if (R < 0 || R > SVOSLAM_MAX_RADIUS_CELLS) return SVOSLAM_ERR_INVALID_ARG;  // R^2 + 2^30 fits an int32
@@ -200,7 +200,10 @@ int pool_distance_field(svoslam_workspace *ws, const svoslam_pool *pool, int dep
   const int off_x = (int)(origin[0] - lo[0]), off_y = (int)(origin[1] - lo[1]), off_z = (int)(origin[2] - lo[2]);
   LaunchEvents timed;
   timed.on = launch_ms != nullptr;
-  StageScope query(kStageQuery, stream);
+  // a caller that goes on after the field (map_reach.hip) owns the bracket: it is opened here, where nothing can be refused any
+  // more, and closed by the caller
+  if (outer_bracket) (void)stage_begin(kStageQuery, stream, outer_bracket);
+  StageScope query(outer_bracket ? -1 : (int)kStageQuery, stream);
   SVO_TRY(timed.mark(stream));
   field_raster_kernel<<<cdiv(words, 4), 256, 0, stream>>>(pool->d_data, depth, (int)lo[0], (int)lo[1], (int)lo[2], (int)(lo[0] + len[0]),
                                                           (int)wpr, (int)len[1], words, bits);
