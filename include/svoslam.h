@@ -544,6 +544,33 @@ int svoslam_pool_reach_field(svoslam_workspace *ws, const svoslam_pool *pool, in
  * control record with the tile flags; NULL / 0 before the first call), as svoslam_workspace_field_buffers shows the distance
  * field's.  Host only. */
 int svoslam_workspace_reach_buffers(const svoslam_workspace *ws, void *d_ptrs[2], uint64_t bytes[2]);
+/* The library's own sort and scan, exposed for tests and tools (no reference counterpart).  Every map operation sorts Morton keys
+ * with the stable LSD radix sort of csrc/radix_sort.hip and compacts with its exclusive scan; these two calls reach them with
+ * arguments of the caller's choosing, where the map's calls choose the form and the digit width from n.  All arrays are in device
+ * memory; both calls are asynchronous on `stream` and use grow-only slots of the workspace (the sort's ping-pong arrays and
+ * histograms, the scan's chunk sums), so the workspace's sort phase outcome (svoslam_svo_fuse_sort, _adopt_sorted) is void after
+ * svoslam_sort_words.
+ *   svoslam_sort_words sorts n 64-bit words.  Stable: R1, equal keys leave in the order they came in.
+ *     idx_bits >= 0, the packed form: a word is key << idx_bits | index.  The words are sorted on their key bits
+ *       [idx_bits, idx_bits + key_bits) in passes of digit_bits bits or fewer (1..11; 0: the width the map's calls take for n
+ *       elements), tiles of 2048 words.  d_keys_out[i] = word >> idx_bits of the i-th sorted word -- bits above the key included,
+ *       which order nothing -- and, if want_vals != 0, d_vals_out[i] = the low 32 bits of word & (2^idx_bits - 1).  d_vals is
+ *       ignored.  idx_bits = 0: the keys alone (the voxel-grid form).
+ *     idx_bits == -1, the pair form: the words are sorted on bits [0, key_bits) in 8-bit passes, tiles of 1024, carrying a 32-bit
+ *       value each: d_vals[i], or i where d_vals is NULL.  d_keys_out = the whole words in sorted order; d_vals_out = the carried
+ *       values, if want_vals != 0.  digit_bits is not used.
+ *     d_vals_out may be NULL when want_vals == 0.  The outputs may be the inputs.
+ *     SVOSLAM_ERR_INVALID_ARG: NULL ws; n < 0; with n > 0 a NULL d_words, d_keys_out, or d_vals_out with want_vals != 0;
+ *     key_bits < 1; idx_bits < -1; key_bits + max(idx_bits, 0) > 64; digit_bits outside 0..11.  n == 0 with valid arguments is
+ *     SVOSLAM_OK and launches nothing.
+ *   svoslam_exclusive_scan_u32 replaces d_data[i] by (d_data[0] + ... + d_data[i - 1]) mod 2^32, in place, and writes the sum of
+ *     all n elements mod 2^32 to *d_total (device memory).  n <= 8192 is one workgroup's loop; longer arrays are scanned in chunks
+ *     of 2048 on any number of workgroups.  n == 0 writes *d_total = 0 (d_data may then be NULL).  SVOSLAM_ERR_INVALID_ARG: NULL
+ *     ws or d_total, NULL d_data with n > 0, n > 2^32 - 2048. */
+int svoslam_sort_words(svoslam_workspace *ws, const unsigned long long *d_words, const uint32_t *d_vals, int32_t n, int32_t key_bits,
+                       int32_t idx_bits, int32_t digit_bits, int32_t want_vals, unsigned long long *d_keys_out, uint32_t *d_vals_out,
+                       void *stream);
+int svoslam_exclusive_scan_u32(svoslam_workspace *ws, uint32_t *d_data, uint32_t n, uint32_t *d_total, void *stream);
 /* device allocation / copies for callers that do not link the HIP runtime themselves (blocking copies) */
 int svoslam_malloc(void **d_ptr, size_t bytes);
 int svoslam_memcpy_h2d(void *d_dst, const void *h_src, size_t bytes);

@@ -195,6 +195,8 @@ SIGNATURES = {
     "svoslam_pool_reach_field": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _vp, _i32, _vp,
                                            C.POINTER(_ReachStats), _vp]),
     "svoslam_workspace_reach_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "svoslam_sort_words": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "svoslam_exclusive_scan_u32": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp]),
     "svoslam_malloc": (C.c_int, [C.POINTER(_vp), C.c_size_t]),
     "svoslam_cone_trace_svo": (C.c_int, [_vp, _i32, _i32, _f32, _fp, _vp, _fp, _f32, _i32, _vp, _vp]),
     "svoslam_cone_trace_svo_band": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _f32, _fp, _vp, _fp, _f32, _i32, _vp, _vp]),
@@ -555,6 +557,31 @@ def svo_fuse_merge_sorted(keys_lists, idx_lists, keys_out, idx_out):
 def svo_fuse_export_sorted(ws, n, keys_out, idx_out):
     """the outcome of the workspace's sort phase -> keys_out (int64 cuda tensor [n]), idx_out (int32 cuda tensor [n])"""
     check(lib().svoslam_svo_fuse_export_sorted(ws._h, int(n), _ptr(keys_out), _ptr(idx_out), _stream()))
+
+
+def sort_words(ws, words, key_bits, idx_bits, digit_bits=0, want_vals=True, vals=None, keys_out=None, vals_out=None):
+    """svoslam_sort_words: the library's stable radix sort on `words` (int64 cuda tensor [n]).  idx_bits >= 0: the packed form
+    (key << idx_bits | index; digit_bits 1..11, 0 = by size); idx_bits == -1: the pair form carrying `vals` (int32 cuda tensor
+    [n]; None: 0..n-1).  -> (keys, vals) as int64 / int32 cuda tensors (vals None when want_vals is false)"""
+    import torch
+    n = int(words.shape[0])
+    if keys_out is None:
+        keys_out = torch.empty(n, dtype=torch.int64, device=words.device)
+    if vals_out is None and want_vals:
+        vals_out = torch.empty(n, dtype=torch.int32, device=words.device)
+    check(lib().svoslam_sort_words(ws._h, _ptr(words), _ptr(vals), n, int(key_bits), int(idx_bits), int(digit_bits), 1 if want_vals else 0,
+                                   _ptr(keys_out), _ptr(vals_out), _stream()))
+    return keys_out, vals_out
+
+
+def exclusive_scan_u32(ws, data, total=None):
+    """svoslam_exclusive_scan_u32: `data` (int32 cuda tensor [n], read as uint32) becomes its exclusive prefix sums mod 2^32, in
+    place.  -> total (int32 cuda tensor [1]: the sum mod 2^32)"""
+    import torch
+    if total is None:
+        total = torch.empty(1, dtype=torch.int32, device=data.device)
+    check(lib().svoslam_exclusive_scan_u32(ws._h, _ptr(data), int(data.shape[0]), _ptr(total), _stream()))
+    return total
 
 
 def svo_fuse_adopt_sorted(ws, keys, idx, max_depth):

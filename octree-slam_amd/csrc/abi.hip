@@ -16,6 +16,7 @@
 #include "model_depth.hpp"
 #include "frame_io.hpp"
 #include "pool_grid.hpp"
+#include "radix_sort.hpp"
 #include "stage_timing.hpp"
 #include "svo_build.hpp"
 #include "workspace.hpp"
@@ -421,6 +422,22 @@ int svoslam_workspace_reach_buffers(const svoslam_workspace *ws, void *d_ptrs[2]
   if (!ws || !d_ptrs || !bytes) return SVOSLAM_ERR_INVALID_ARG;
   const svoslam::DeviceBuffer *slots[2] = {&ws->reach_bits, &ws->reach_flags};
   for (int k = 0; k < 2; k++) { d_ptrs[k] = slots[k]->ptr; bytes[k] = slots[k]->bytes; }
+  return SVOSLAM_OK;
+}
+
+// the library's own sort and scan with the caller's arguments (tests and tools)
+int svoslam_sort_words(svoslam_workspace *ws, const unsigned long long *d_words, const uint32_t *d_vals, int32_t n, int32_t key_bits,
+                       int32_t idx_bits, int32_t digit_bits, int32_t want_vals, unsigned long long *d_keys_out, uint32_t *d_vals_out,
+                       void *stream) {
+  NEED_DEVICE();
+  return sort_words(ws, d_words, d_vals, n, key_bits, idx_bits, digit_bits, want_vals != 0, d_keys_out, d_vals_out, S(stream));
+}
+int svoslam_exclusive_scan_u32(svoslam_workspace *ws, uint32_t *d_data, uint32_t n, uint32_t *d_total, void *stream) {
+  NEED_DEVICE();
+  if (!ws || !d_total || (n > 0 && !d_data)) return SVOSLAM_ERR_INVALID_ARG;
+  if (n > 0xFFFFF800u) return SVOSLAM_ERR_INVALID_ARG;  // the last chunk's element numbers must not wrap
+  SVO_TRY(exclusive_scan_u32(ws, d_data, n, d_total, S(stream)));
+  SVO_LAUNCH_CHECK();
   return SVOSLAM_OK;
 }
 

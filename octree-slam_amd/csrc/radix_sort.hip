@@ -458,4 +458,36 @@ int radix_sort_pairs(svoslam_workspace *ws, int n, int num_bits, hipStream_t str
   return SVOSLAM_OK;
 }
 
+// ---- the sort with the caller's arguments (svoslam_sort_words: tests and tools) ------------------------------------------
+// Either form on the caller's words: they are copied into ws->keys_a (the values into ws->vals_a), the workspace slots the
+// internal call expects are reserved as its callers reserve them, and the sorted arrays are copied out on `stream`.
+int sort_words(svoslam_workspace *ws, const unsigned long long *d_words, const unsigned *d_vals, int n, int key_bits, int idx_bits,
+               int digit_bits, bool want_vals, unsigned long long *d_keys_out, unsigned *d_vals_out, hipStream_t stream) {
+  if (!ws || n < 0 || key_bits < 1 || idx_bits < -1 || key_bits + (idx_bits > 0 ? idx_bits : 0) > 64) return SVOSLAM_ERR_INVALID_ARG;
+  if (digit_bits < 0 || digit_bits > kPackedMaxBits) return SVOSLAM_ERR_INVALID_ARG;
+  if (n > 0 && (!d_words || !d_keys_out || (want_vals && !d_vals_out))) return SVOSLAM_ERR_INVALID_ARG;
+  if (n == 0) return SVOSLAM_OK;
+  // the slots are about to be overwritten (and may move): a sort phase's outcome on this workspace is gone
+  ws->sorted_keys = nullptr; ws->sorted_idx = nullptr; ws->planned_n = -1;
+  SVO_TRY(ws->keys_a.reserve((size_t)n * 8));
+  SVO_TRY(ws->keys_b.reserve((size_t)n * 8));
+  SVO_TRY(ws->vals_a.reserve((size_t)n * 4));
+  SVO_TRY(ws->vals_b.reserve((size_t)n * 4));
+  SVO_HIP(hipMemcpyAsync(ws->keys_a.ptr, d_words, (size_t)n * 8, hipMemcpyDeviceToDevice, stream));
+  unsigned long long *skey = nullptr;
+  unsigned *sval = nullptr;
+  if (idx_bits >= 0) {
+    const int bits = digit_bits ? digit_bits : radix_packed_digit_bits_for(n);
+    SVO_TRY(radix_sort_packed_ex(ws, n, key_bits, idx_bits, bits, false, want_vals, stream, &skey, &sval));
+  } else {
+    SVO_TRY(ws->tile_hist.reserve((size_t)256 * radix_sort_num_tiles(n) * 4));
+    SVO_TRY(ws->reserve_small());  // the digit totals: its first 256 words
+    if (d_vals) SVO_HIP(hipMemcpyAsync(ws->vals_a.ptr, d_vals, (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
+    SVO_TRY(radix_sort_pairs(ws, n, key_bits, stream, &skey, &sval, d_vals == nullptr));
+  }
+  SVO_HIP(hipMemcpyAsync(d_keys_out, skey, (size_t)n * 8, hipMemcpyDeviceToDevice, stream));
+  if (want_vals) SVO_HIP(hipMemcpyAsync(d_vals_out, sval, (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
+  return SVOSLAM_OK;
+}
+
 }  // namespace svoslam

@@ -37,4 +37,9 @@ void row_scan_rows(unsigned *rows, int num_tiles, unsigned *totals, hipStream_t 
 void row_scan_rows1(unsigned *row, int num_tiles, unsigned *total, hipStream_t stream);
 // in-place exclusive scan of data[0..n) on any number of workgroups; *total (device) = the sum
 int exclusive_scan_u32(svoslam_workspace *ws, unsigned *data, unsigned n, unsigned *total, hipStream_t stream);
+// svoslam_sort_words (include/svoslam.h): either sort on the caller's device arrays, through the workspace's slots.
+// idx_bits >= 0: radix_sort_packed_ex without a first histogram (digit_bits 0 = radix_packed_digit_bits_for(n));
+// idx_bits == -1: radix_sort_pairs, values iota (d_vals NULL) or d_vals.
+int sort_words(svoslam_workspace *ws, const unsigned long long *d_words, const unsigned *d_vals, int n, int key_bits, int idx_bits,
+               int digit_bits, bool want_vals, unsigned long long *d_keys_out, unsigned *d_vals_out, hipStream_t stream);
 }  // namespace svoslam
