@@ -173,8 +173,10 @@ def walk(words, target, lod, center, size):
     return node, end
 
 
-def census(words, w, h, fov, inv_view, center, size):
-    """image, steps, levels of the reference's march, and the census of its samples (a dict of counts)"""
+def lockstep(words, w, h, fov, inv_view, center, size, result):
+    """the reference's march with all rays of an image in lockstep, one iteration per step: yields (rays, target, lod, node, end,
+    retire, out) of the rays still marching -- their pixel indices, samples, LODs, the node and level each walk ends on, and which
+    of them retire on this sample or leave the range behind it.  `result` receives img, steps and levels (final when exhausted)"""
     tanf = ctypes.CDLL("libm.so.6").tanf
     tanf.restype, tanf.argtypes = ctypes.c_float, [ctypes.c_float]
     words = np.ascontiguousarray(words, np.uint32)
@@ -191,30 +193,18 @@ def census(words, w, h, fov, inv_view, center, size):
     ray = START_DIST * (d * (F(1.0) / _length(d))[:, None])
     img = np.zeros((w * h, 4), np.uint8)
     active = np.arange(w * h)
-    steps = levels = 0
+    result.update(img=img.reshape(h, w, 4), steps=0, levels=0)
     size_m, size_e = np.frexp(np.float64(size))
-    sat0 = alpha_of(words, 0) >= SATURATED
-    counts = dict(lod_le0=0, lod_le0_over_children_other_saturation=0, lod1_octant0=0, st1_octant0_lod_ge8=0, lod_le_m1=0, pixels=w * h)
     while len(active):
-        steps += len(active)
-        assert steps <= MAX_ORACLE_STEPS
+        result["steps"] += len(active)
+        assert result["steps"] <= MAX_ORACLE_STEPS
         r = ray[active]
         target = origin[None, :] + r
         ray_len = _length(r)
         mb, eb = np.frexp((ray_len * pix_scale).astype(np.float64))
         lod = ((size_e - eb) + (size_m > mb)).astype(np.int64)       # ceil(log2) of the real quotient (R5)
         node, end = walk(words, target, lod, center, size)
-        levels += int(np.maximum(end, 0).sum())
-        # ---- the census of these samples ----
-        le0 = lod <= 0
-        counts["lod_le0"] += int(le0.sum())
-        if le0.any():
-            n8, e8 = walk(words, target[le0], np.full(int(le0.sum()), 8, np.int64), center, size)
-            deep = (e8 == 8) & ((words[2 * n8] & FLAG) != 0)
-            counts["lod_le0_over_children_other_saturation"] += int((deep & (((words[2 * n8 + 1] >> 24) >= SATURATED) != sat0)).sum())
-        counts["lod1_octant0"] += int(((lod == 1) & (node == 0)).sum())
-        counts["st1_octant0_lod_ge8"] += int(((lod >= 8) & (end == 1) & (node == 0)).sum())
-        counts["lod_le_m1"] += int((lod <= -1).sum())
+        result["levels"] += int(np.maximum(end, 0).sum())
         # ---- the sample's value, retirement, advance (:107-138) ----
         val = words[2 * node + 1].astype(np.int64)
         alpha = (val >> 24) - 127
@@ -232,5 +222,24 @@ def census(words, w, h, fov, inv_view, center, size):
                 sc = F(127.0) / (alpha[out] & 0xFF).astype(F)
                 img[active[out], :3] = _f2u8(v[out].astype(F) * sc[:, None])
             img[active[out], 3] = 255
+        yield active, target, lod, node, end, retire, out
         active = active[~retire & ~out]
-    return img.reshape(h, w, 4), steps, levels, counts
+
+
+def census(words, w, h, fov, inv_view, center, size):
+    """image, steps, levels of the reference's march, and the census of its samples (a dict of counts)"""
+    words = np.ascontiguousarray(words, np.uint32)
+    sat0 = alpha_of(words, 0) >= SATURATED
+    counts = dict(lod_le0=0, lod_le0_over_children_other_saturation=0, lod1_octant0=0, st1_octant0_lod_ge8=0, lod_le_m1=0, pixels=w * h)
+    result = {}
+    for _, target, lod, node, end, _, _ in lockstep(words, w, h, fov, inv_view, center, size, result):
+        le0 = lod <= 0
+        counts["lod_le0"] += int(le0.sum())
+        if le0.any():
+            n8, e8 = walk(words, target[le0], np.full(int(le0.sum()), 8, np.int64), center, size)
+            deep = (e8 == 8) & ((words[2 * n8] & FLAG) != 0)
+            counts["lod_le0_over_children_other_saturation"] += int((deep & (((words[2 * n8 + 1] >> 24) >= SATURATED) != sat0)).sum())
+        counts["lod1_octant0"] += int(((lod == 1) & (node == 0)).sum())
+        counts["st1_octant0_lod_ge8"] += int(((lod >= 8) & (end == 1) & (node == 0)).sum())
+        counts["lod_le_m1"] += int((lod <= -1).sum())
+    return result["img"], result["steps"], result["levels"], counts
