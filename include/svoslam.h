@@ -544,6 +544,46 @@ int svoslam_pool_reach_field(svoslam_workspace *ws, const svoslam_pool *pool, in
  * control record with the tile flags; NULL / 0 before the first call), as svoslam_workspace_field_buffers shows the distance
  * field's.  Host only. */
 int svoslam_workspace_reach_buffers(const svoslam_workspace *ws, void *d_ptrs[2], uint64_t bytes[2]);
+/* The component labels of a map region (no reference counterpart; specification here and in DESIGN.md section 17): for every cell of
+ * a box of cells that belongs to a set S, a label that names its connected component of S inside the region, and optionally that
+ * component's size -- "are A and B connected at all" is labels[a] == labels[b], "drop floaters under k cells" is sizes >= k.
+ * Exact, in integers.
+ *   d, N, the occupied set and the region are exactly those of svoslam_pool_distance_field: cells at depth d = max_depth, the
+ *     region origin_cell .. origin_cell + dims inside the root.
+ *   The set S: with r = clearance_cells (0..SVOSLAM_MAX_RADIUS_CELLS), T is svoslam_pool_reach_field's traversable set: the region
+ *     cells where svoslam_pool_distance_field with radius_cells = r writes -1.  which = SVOSLAM_COMPONENTS_FREE: S = T.  which =
+ *     SVOSLAM_COMPONENTS_SOLID: S = the region's cells that are not in T -- at r = 0 the occupied cells of the region, at r > 0 the
+ *     occupied cells dilated by r (occupied cells up to r outside the region count).
+ *   Components: two cells of S are connected iff a chain of face-neighbour moves joins them whose every cell is in S AND IN THE
+ *     REGION.  Connectivity is 6, as in the reach field: cells that touch only by an edge or a corner are not connected by that
+ *     contact.  A caller who wants looser clustering of occupied cells asks for SOLID with r = 1, which joins cells up to two
+ *     apart; 26-connectivity is not offered.
+ *   Output: d_labels, dims[0] * dims[1] * dims[2] values of type int32 in device memory, x fastest, indexed as d_dist2 is.  The
+ *     value at q is -1 if q is not in S; otherwise the SMALLEST OUTPUT INDEX of any cell of q's component.  The labels are
+ *     therefore canonical: labels[labels[q]] == labels[q], labels[q] <= q, and the result does not depend on scheduling.
+ *     d_sizes (may be NULL): the same shape; at every cell of S the number of cells of its component, elsewhere 0.  stats (may be
+ *     NULL): components = the number of components; largest = the size of the largest one, 0 if d_sizes is NULL or S is empty;
+ *     tile_passes and unions are diagnostics with no specified value (the sweeps inside tiles, the links made across tile
+ *     faces).  Only these values are specified, not how they are computed.
+ *   Conventions: those of svoslam_pool_distance_field -- any pool; pending asynchronous fusions are drained first; a deferred
+ *     commit's pool is read in its old state; the intermediates (the distance field's, the bit rows of S and a 32-byte control
+ *     record) live in grow-only slots of the workspace, so a second call of the same size allocates nothing.  THE CALL IS
+ *     ASYNCHRONOUS ON `stream` WHEN stats IS NULL: nothing is read back, there are no rounds.  With stats it blocks for one
+ *     readback of the control record at the end.
+ *   Errors: a zero entry of dims is SVOSLAM_OK and launches nothing, if the other arguments are valid.  SVOSLAM_ERR_INVALID_ARG:
+ *     those of svoslam_pool_distance_field (clearance_cells for radius_cells, d_labels for d_dist2), or `which` outside {0, 1}.
+ *     SVOSLAM_ERR_POOL_LIMIT: the limits of svoslam_pool_distance_field with radius_cells = clearance_cells, or more than 2^24 - 1
+ *     tiles of 64 x 8 x 8 cells, decided before anything is allocated or written.  SVOSLAM_ERR_OOM: an allocation failed; the
+ *     slots the call grew are released, after the stream has drained. */
+#define SVOSLAM_COMPONENTS_FREE  0
+#define SVOSLAM_COMPONENTS_SOLID 1
+typedef struct { int32_t components, largest, tile_passes, unions; } svoslam_component_stats;
+int svoslam_pool_label_components(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                                  const int32_t dims[3], int32_t clearance_cells, int32_t which, int32_t *d_labels,
+                                  int32_t *d_sizes /* may be NULL */, svoslam_component_stats *stats /* may be NULL */, void *stream);
+/* diagnostics: the device pointers and sizes in bytes of the workspace's two component slots (the bit rows of S; the control
+ * record; NULL / 0 before the first call), as svoslam_workspace_reach_buffers shows the reach field's.  Host only. */
+int svoslam_workspace_component_buffers(const svoslam_workspace *ws, void *d_ptrs[2], uint64_t bytes[2]);
 /* The library's own sort and scan, exposed for tests and tools (no reference counterpart).  Every map operation sorts Morton keys
  * with the stable LSD radix sort of csrc/radix_sort.hip and compacts with its exclusive scan; these two calls reach them with
  * arguments of the caller's choosing, where the map's calls choose the form and the digit width from n.  All arrays are in device
@@ -728,7 +768,7 @@ int svoslam_cone_trace_timing_read(float *h_ms_sum, int32_t *h_launches);
 #define SVOSLAM_STAGE_SURFACE_BFS 9    /* extract_surface_mesh: the occupied cells (incl. one readback per level) */
 #define SVOSLAM_STAGE_SURFACE_FACES 10 /* extract_surface_mesh: face masks + scan (incl. the count readback) | emission: two brackets per call, the host's allocations between them are outside */
 #define SVOSLAM_STAGE_SURFACE_WELD 11  /* extract_surface_mesh: corner sort + run heads + scan (incl. the count readback) | scatter: two brackets per call likewise */
-#define SVOSLAM_STAGE_QUERY 12         /* svoslam_pool_cast_rays / _query_points / _count_boxes / _nearest_occupied: the kernel, one bracket per call; svoslam_pool_distance_field: its four launches, one bracket per call; svoslam_pool_reach_field: the field's launches and every launch and readback of the relaxation, one bracket per call */
+#define SVOSLAM_STAGE_QUERY 12         /* svoslam_pool_cast_rays / _query_points / _count_boxes / _nearest_occupied: the kernel, one bracket per call; svoslam_pool_distance_field: its four launches, one bracket per call; svoslam_pool_reach_field: the field's launches and every launch and readback of the relaxation, one bracket per call; svoslam_pool_label_components: the field's launches and its own, one bracket per call */
 #define SVOSLAM_STAGE_COUNT 13
 int svoslam_stage_timing(uint32_t mask);
 int svoslam_stage_timing_read(int32_t stage, float *h_ms_sum, int32_t *h_pairs);

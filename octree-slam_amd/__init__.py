@@ -50,6 +50,10 @@ class _ReachStats(C.Structure):
     _fields_ = [("rounds", C.c_int32), ("tile_runs", C.c_int32), ("seeds_used", C.c_int32)]
 
 
+class _ComponentStats(C.Structure):
+    _fields_ = [("components", C.c_int32), ("largest", C.c_int32), ("tile_passes", C.c_int32), ("unions", C.c_int32)]
+
+
 class MeshStruct(C.Structure):
     _fields_ = [("vbo", C.POINTER(C.c_float)), ("tbo", C.POINTER(C.c_float)), ("n_tris", C.c_int32), ("tbosize", C.c_int32),
                 ("bbox0", C.c_float * 3), ("bbox1", C.c_float * 3)]
@@ -195,6 +199,9 @@ SIGNATURES = {
     "svoslam_pool_reach_field": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _vp, _i32, _vp,
                                            C.POINTER(_ReachStats), _vp]),
     "svoslam_workspace_reach_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "svoslam_pool_label_components": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _vp, _vp,
+                                                C.POINTER(_ComponentStats), _vp]),
+    "svoslam_workspace_component_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
     "svoslam_sort_words": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "svoslam_exclusive_scan_u32": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp]),
     "svoslam_malloc": (C.c_int, [C.POINTER(_vp), C.c_size_t]),
@@ -371,6 +378,12 @@ class Workspace:
         """svoslam_workspace_reach_buffers: [(device pointer, bytes)] of the two reach-field slots (diagnostics)"""
         ptrs, sizes = (_vp * 2)(), (C.c_uint64 * 2)()
         check(lib().svoslam_workspace_reach_buffers(self._h, ptrs, sizes))
+        return [(int(ptrs[k] or 0), int(sizes[k])) for k in range(2)]
+
+    def component_buffers(self):
+        """svoslam_workspace_component_buffers: [(device pointer, bytes)] of the two component slots (diagnostics)"""
+        ptrs, sizes = (_vp * 2)(), (C.c_uint64 * 2)()
+        check(lib().svoslam_workspace_component_buffers(self._h, ptrs, sizes))
         return [(int(ptrs[k] or 0), int(sizes[k])) for k in range(2)]
 
     def __del__(self):
@@ -846,6 +859,35 @@ def reach_field(ws, pool, max_depth, origin, dims, clearance_cells, seeds, as_te
     if stats is not None:
         stats.update(rounds=int(st.rounds), tile_runs=int(st.tile_runs), seeds_used=int(st.seeds_used))
     return out if as_tensor else out.cpu().numpy()
+
+
+COMPONENTS_FREE, COMPONENTS_SOLID = 0, 1                                # include/svoslam.h SVOSLAM_COMPONENTS_*
+
+
+def label_components(ws, pool, max_depth, origin, dims, clearance_cells, solid=False, sizes=False, as_tensor=False, stats=None):
+    """svoslam_pool_label_components: the 6-connected components, inside the region origin[3] .. origin + dims[3] (cells at max_depth,
+    x y z), of the cells with no occupied cell within clearance_cells (those where distance_field with that radius is -1), or with
+    `solid` of the region's other cells (at clearance 0 the occupied cells).  -> int32 [nz, ny, nx]: -1 where the cell is not in the
+    set, otherwise the smallest output index ((z * ny + y) * nx + x) of any cell of its component; with `sizes` the pair (labels,
+    sizes), sizes the cells of the component at every cell of the set and 0 elsewhere.  numpy arrays, or with as_tensor cuda tensors,
+    in which case nothing is synchronised -- unless `stats` is given: a dict that receives components, largest (0 without `sizes`),
+    tile_passes and unions, for which the call blocks on one readback."""
+    import torch
+    o, n = [int(v) for v in origin], [int(v) for v in dims]
+    if len(o) != 3 or len(n) != 3:
+        raise ValueError("origin and dims are three cells each (x, y, z)")
+    shape = [max(v, 0) for v in reversed(n)]
+    out = torch.empty(shape, dtype=torch.int32, device="cuda")
+    count = torch.empty(shape, dtype=torch.int32, device="cuda") if sizes else None
+    st = _ComponentStats()
+    check(lib().svoslam_pool_label_components(ws._h, C.byref(pool._p), int(max_depth), (_i32 * 3)(*o), (_i32 * 3)(*n), int(clearance_cells),
+                                              COMPONENTS_SOLID if solid else COMPONENTS_FREE, _ptr(out), _ptr(count),
+                                              C.byref(st) if stats is not None else None, _stream()))
+    if stats is not None:
+        stats.update(components=int(st.components), largest=int(st.largest), tile_passes=int(st.tile_passes), unions=int(st.unions))
+    if not as_tensor:
+        out, count = out.cpu().numpy(), count.cpu().numpy() if sizes else None
+    return (out, count) if sizes else out
 
 
 def box_to_cells(max_depth, center, edge_length, box):

@@ -8,6 +8,7 @@
 #include "cone_trace.hpp"
 #include "icp.hpp"
 #include "image_kernels.hpp"
+#include "map_components.hpp"
 #include "map_field.hpp"
 #include "map_query.hpp"
 #include "map_reach.hpp"
@@ -421,6 +422,20 @@ int svoslam_pool_reach_field(svoslam_workspace *ws, const svoslam_pool *pool, in
 int svoslam_workspace_reach_buffers(const svoslam_workspace *ws, void *d_ptrs[2], uint64_t bytes[2]) {
   if (!ws || !d_ptrs || !bytes) return SVOSLAM_ERR_INVALID_ARG;
   const svoslam::DeviceBuffer *slots[2] = {&ws->reach_bits, &ws->reach_flags};
+  for (int k = 0; k < 2; k++) { d_ptrs[k] = slots[k]->ptr; bytes[k] = slots[k]->bytes; }
+  return SVOSLAM_OK;
+}
+
+int svoslam_pool_label_components(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                                  const int32_t dims[3], int32_t clearance_cells, int32_t which, int32_t *d_labels, int32_t *d_sizes,
+                                  svoslam_component_stats *stats, void *stream) {
+  NEED_DEVICE();
+  return pool_label_components(ws, pool, max_depth, origin_cell, dims, clearance_cells, which, d_labels, d_sizes, stats, S(stream));
+}
+
+int svoslam_workspace_component_buffers(const svoslam_workspace *ws, void *d_ptrs[2], uint64_t bytes[2]) {
+  if (!ws || !d_ptrs || !bytes) return SVOSLAM_ERR_INVALID_ARG;
+  const svoslam::DeviceBuffer *slots[2] = {&ws->comp_bits, &ws->comp_ctl};
   for (int k = 0; k < 2; k++) { d_ptrs[k] = slots[k]->ptr; bytes[k] = slots[k]->bytes; }
   return SVOSLAM_OK;
 }

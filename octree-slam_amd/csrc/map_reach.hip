@@ -253,13 +253,6 @@ __global__ __launch_bounds__(256) void reach_finish_kernel(int32_t *__restrict__
   steps[at] = !((bits[word] >> lane) & 1ull) ? -2 : v == kNone ? -1 : v;
 }
 
-struct AdoptedBracket {  // pool_distance_field opens the call's bracket; it is closed when the call leaves
-  long long token = -1;
-  hipStream_t s;
-  explicit AdoptedBracket(hipStream_t stream) : s(stream) {}
-  ~AdoptedBracket() { (void)stage_end(kStageQuery, token, s); }
-};
-
 }  // namespace
 
 int pool_reach_field(svoslam_workspace *ws, const svoslam_pool *pool, int depth, const int32_t origin[3], const int32_t dims[3],

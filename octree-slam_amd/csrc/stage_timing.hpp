@@ -23,7 +23,7 @@ enum Stage {
   kStageSurfaceBfs = SVOSLAM_STAGE_SURFACE_BFS,      // svo_surface.hip: the occupied cells (bfs_occupied_keys, incl. one readback per level)
   kStageSurfaceFaces = SVOSLAM_STAGE_SURFACE_FACES,  // svo_surface.hip: face masks + scan (incl. the count readback) | emission: two brackets per call
   kStageSurfaceWeld = SVOSLAM_STAGE_SURFACE_WELD,    // svo_surface.hip: corner sort + run heads + scan (incl. the count readback) | scatter: two brackets per call
-  kStageQuery = SVOSLAM_STAGE_QUERY,               // map_query.hip, map_volume.hip, map_field.hip, map_reach.hip: one bracket per call around the query's kernel(s)
+  kStageQuery = SVOSLAM_STAGE_QUERY,               // map_query.hip, map_volume.hip, map_field.hip, map_reach.hip, map_components.hip: one bracket per call around the query's kernel(s)
   kStageCount = SVOSLAM_STAGE_COUNT
 };
 
@@ -41,6 +41,13 @@ struct StageScope {  // brackets a scope; tolerant of early returns
   int stage; hipStream_t s; long long token = -1;
   StageScope(int st, hipStream_t stream) : stage(st), s(stream) { (void)stage_begin(stage, s, &token); }
   ~StageScope() { (void)stage_end(stage, token, s); }
+};
+
+struct AdoptedBracket {  // a kStageQuery bracket that pool_distance_field opens into `token` for a caller that goes on after
+  long long token = -1;  // the field; it is closed when the caller leaves
+  hipStream_t s;
+  explicit AdoptedBracket(hipStream_t stream) : s(stream) {}
+  ~AdoptedBracket() { (void)stage_end(kStageQuery, token, s); }
 };
 
 }  // namespace svoslam
