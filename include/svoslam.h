@@ -584,6 +584,45 @@ int svoslam_pool_label_components(svoslam_workspace *ws, const svoslam_pool *poo
 /* diagnostics: the device pointers and sizes in bytes of the workspace's two component slots (the bit rows of S; the control
  * record; NULL / 0 before the first call), as svoslam_workspace_reach_buffers shows the reach field's.  Host only. */
 int svoslam_workspace_component_buffers(const svoslam_workspace *ws, void *d_ptrs[2], uint64_t bytes[2]);
+/* The nearest-cell field of a map region (no reference counterpart; specification here and in DESIGN.md section 18): for every cell
+ * of a box of cells the squared distance to the nearest cell of a target set AND that cell, the witness -- what the gradient of a
+ * distance field, a Voronoi skeleton, "which obstacle is nearest" (labels[witness] of svoslam_pool_label_components) and the colour
+ * of an offset surface are made of, and what cannot be rebuilt from the distances without searching again.  Exact, in integers.
+ *   d, N, the occupied set, the region, the output order (x fastest) and R = radius_cells (0..SVOSLAM_MAX_RADIUS_CELLS) are exactly
+ *     those of svoslam_pool_distance_field.
+ *   Target set A: which = SVOSLAM_NEAREST_OCCUPIED: the occupied cells of the whole root.  which = SVOSLAM_NEAREST_FREE: the cells
+ *     of the root that are not occupied; nothing outside the root is a cell, so a fully occupied root has an empty A.  Target cells
+ *     up to R outside the region count, as they do for the distance field.
+ *   Value at q: D = the minimum of (cx - qx)^2 + (cy - qy)^2 + (cz - qz)^2 over c in A.  If D > R^2, or A is empty: dist2 = -1,
+ *     cell = all ones, node = -1, color = 0.  Otherwise dist2 = D and cell = x | y << 16 | z << 32 of the witness: the cell of A at
+ *     squared distance D with the SMALLEST z, THEN THE SMALLEST y, THEN THE SMALLEST x, in absolute cell coordinates.  For OCCUPIED
+ *     dist2 equals svoslam_pool_nearest_occupied's (for a point inside cell q) and svoslam_pool_distance_field's.  The tie rule is
+ *     NOT svoslam_pool_nearest_occupied's lowest Morton code: the cell can differ from that call's, but only among equally near
+ *     cells.  (It is the rule three separable passes give when each prefers the lower coordinate.)  The signed distance of an ESDF
+ *     is +sqrt(dist2 OCCUPIED) at a free cell and -sqrt(dist2 FREE) at an occupied one.
+ *   d_node, d_color: for OCCUPIED the level-d node of the witness and its colour word, what svoslam_pool_cast_rays reports for that
+ *     cell.  For FREE both must be NULL: a free cell has no level-d node in general.
+ *   Outputs: d_dist2, d_cell, d_node, d_color, each dims[0] * dims[1] * dims[2] values in device memory, indexed as
+ *     svoslam_pool_distance_field's d_dist2.  Every one of them may be NULL; with a non-empty region not all.  Only the values are
+ *     specified, not how they are computed.
+ *   Conventions: those of svoslam_pool_distance_field -- any pool (svoslam_pool_set_nodes words included); asynchronous on `stream`,
+ *     nothing is read back; pending asynchronous fusions are drained first; a pool whose deferred commit waits for its apply is
+ *     read in its old state.  The intermediates live in three grow-only workspace slots of their own (the bit rows of A on the
+ *     inflated region; the values after the x, y and z pass; one 16-bit index per pass), so a second call of the same size
+ *     allocates nothing, and the distance field's slots are never touched.
+ *   Errors: a zero entry of dims is SVOSLAM_OK and launches nothing, if the other arguments are valid.  SVOSLAM_ERR_INVALID_ARG:
+ *     those of svoslam_pool_distance_field; `which` outside {0, 1}; FREE with a d_node or d_color; with a non-empty region all four
+ *     outputs NULL.  SVOSLAM_ERR_POOL_LIMIT: under svoslam_pool_distance_field's conditions, decided before anything is allocated.
+ *     SVOSLAM_ERR_OOM: an allocation failed; nothing the call grew stays behind. */
+#define SVOSLAM_NEAREST_OCCUPIED 0
+#define SVOSLAM_NEAREST_FREE     1
+int svoslam_pool_nearest_field(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                               const int32_t dims[3], int32_t radius_cells, int32_t which, int32_t *d_dist2 /* may be NULL */,
+                               uint64_t *d_cell /* may be NULL */, int32_t *d_node /* may be NULL */, uint32_t *d_color /* may be NULL */,
+                               void *stream);
+/* diagnostics: the device pointers and sizes in bytes of the workspace's three nearest-cell slots (the bit rows; the values; the
+ * indices; NULL / 0 before the first call), as svoslam_workspace_field_buffers shows the distance field's.  Host only. */
+int svoslam_workspace_nearest_buffers(const svoslam_workspace *ws, void *d_ptrs[3], uint64_t bytes[3]);
 /* The library's own sort and scan, exposed for tests and tools (no reference counterpart).  Every map operation sorts Morton keys
  * with the stable LSD radix sort of csrc/radix_sort.hip and compacts with its exclusive scan; these two calls reach them with
  * arguments of the caller's choosing, where the map's calls choose the form and the digit width from n.  All arrays are in device
@@ -768,7 +807,7 @@ int svoslam_cone_trace_timing_read(float *h_ms_sum, int32_t *h_launches);
 #define SVOSLAM_STAGE_SURFACE_BFS 9    /* extract_surface_mesh: the occupied cells (incl. one readback per level) */
 #define SVOSLAM_STAGE_SURFACE_FACES 10 /* extract_surface_mesh: face masks + scan (incl. the count readback) | emission: two brackets per call, the host's allocations between them are outside */
 #define SVOSLAM_STAGE_SURFACE_WELD 11  /* extract_surface_mesh: corner sort + run heads + scan (incl. the count readback) | scatter: two brackets per call likewise */
-#define SVOSLAM_STAGE_QUERY 12         /* svoslam_pool_cast_rays / _query_points / _count_boxes / _nearest_occupied: the kernel, one bracket per call; svoslam_pool_distance_field: its four launches, one bracket per call; svoslam_pool_reach_field: the field's launches and every launch and readback of the relaxation, one bracket per call; svoslam_pool_label_components: the field's launches and its own, one bracket per call */
+#define SVOSLAM_STAGE_QUERY 12         /* svoslam_pool_cast_rays / _query_points / _count_boxes / _nearest_occupied: the kernel, one bracket per call; svoslam_pool_distance_field: its four launches, one bracket per call; svoslam_pool_reach_field: the field's launches and every launch and readback of the relaxation, one bracket per call; svoslam_pool_label_components: the field's launches and its own, one bracket per call; svoslam_pool_nearest_field: its five launches, one bracket per call */
 #define SVOSLAM_STAGE_COUNT 13
 int svoslam_stage_timing(uint32_t mask);
 int svoslam_stage_timing_read(int32_t stage, float *h_ms_sum, int32_t *h_pairs);

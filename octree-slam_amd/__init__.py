@@ -202,6 +202,9 @@ SIGNATURES = {
     "svoslam_pool_label_components": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _vp, _vp,
                                                 C.POINTER(_ComponentStats), _vp]),
     "svoslam_workspace_component_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "svoslam_pool_nearest_field": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _vp, _vp, _vp,
+                                             _vp, _vp]),
+    "svoslam_workspace_nearest_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
     "svoslam_sort_words": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "svoslam_exclusive_scan_u32": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp]),
     "svoslam_malloc": (C.c_int, [C.POINTER(_vp), C.c_size_t]),
@@ -385,6 +388,12 @@ class Workspace:
         ptrs, sizes = (_vp * 2)(), (C.c_uint64 * 2)()
         check(lib().svoslam_workspace_component_buffers(self._h, ptrs, sizes))
         return [(int(ptrs[k] or 0), int(sizes[k])) for k in range(2)]
+
+    def nearest_buffers(self):
+        """svoslam_workspace_nearest_buffers: [(device pointer, bytes)] of the three nearest-cell slots (diagnostics)"""
+        ptrs, sizes = (_vp * 3)(), (C.c_uint64 * 3)()
+        check(lib().svoslam_workspace_nearest_buffers(self._h, ptrs, sizes))
+        return [(int(ptrs[k] or 0), int(sizes[k])) for k in range(3)]
 
     def __del__(self):
         try:
@@ -888,6 +897,40 @@ def label_components(ws, pool, max_depth, origin, dims, clearance_cells, solid=F
     if not as_tensor:
         out, count = out.cpu().numpy(), count.cpu().numpy() if sizes else None
     return (out, count) if sizes else out
+
+
+NEAREST_OCCUPIED, NEAREST_FREE = 0, 1                                   # include/svoslam.h SVOSLAM_NEAREST_*
+
+
+def nearest_field(ws, pool, max_depth, origin, dims, radius_cells, which=0, want=("dist2", "cell"), as_tensor=False):
+    """svoslam_pool_nearest_field: for every cell of the region origin[3] .. origin + dims[3] (cells at max_depth, x y z) the nearest
+    cell within radius_cells of the occupied cells (which = NEAREST_OCCUPIED) or of the root's cells that are not occupied
+    (NEAREST_FREE); among equally near cells the one with the smallest z, then y, then x.  `want`: the subset of "dist2" (int32,
+    squared cells, -1 = none), "cell" (uint64 x | y << 16 | z << 32, all ones = none), "node" (int32, -1) and "color" (uint32, 0) to
+    compute -- node and color only for NEAREST_OCCUPIED; the others are passed as NULL.  -> a dict of [nz, ny, nx] arrays; with
+    "cell" also "cell_xyz", int32 [nz, ny, nx, 3], -1 where there is none.  numpy arrays, or with as_tensor cuda tensors (cell int64,
+    color int32: the same bits), in which case nothing is synchronised."""
+    import torch
+    o, n = [int(v) for v in origin], [int(v) for v in dims]
+    if len(o) != 3 or len(n) != 3:
+        raise ValueError("origin and dims are three cells each (x, y, z)")
+    fields = {"dist2": (torch.int32, np.int32), "cell": (torch.int64, np.uint64), "node": (torch.int32, np.int32),
+              "color": (torch.int32, np.uint32)}
+    names = tuple(want)
+    for name in names:
+        if name not in fields:
+            raise KeyError("no output %r (have: %s)" % (name, ", ".join(fields)))
+    shape = [max(v, 0) for v in reversed(n)]
+    bufs = {name: torch.empty(shape, dtype=fields[name][0], device="cuda") for name in names}
+    check(lib().svoslam_pool_nearest_field(ws._h, C.byref(pool._p), int(max_depth), (_i32 * 3)(*o), (_i32 * 3)(*n), int(radius_cells),
+                                           int(which), *[_ptr(bufs.get(name)) for name in fields], _stream()))
+    if "cell" in bufs:
+        c = bufs["cell"]
+        xyz = torch.stack([c & 0xFFFF, (c >> 16) & 0xFFFF, (c >> 32) & 0xFFFF], -1).to(torch.int32)
+        bufs["cell_xyz"] = torch.where((c < 0).unsqueeze(-1), torch.full_like(xyz, -1), xyz)
+    if as_tensor:
+        return bufs
+    return {name: b.cpu().numpy().view(fields[name][1]) if name in fields else b.cpu().numpy() for name, b in bufs.items()}
 
 
 def box_to_cells(max_depth, center, edge_length, box):

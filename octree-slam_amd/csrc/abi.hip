@@ -10,6 +10,7 @@
 #include "image_kernels.hpp"
 #include "map_components.hpp"
 #include "map_field.hpp"
+#include "map_nearest.hpp"
 #include "map_query.hpp"
 #include "map_reach.hpp"
 #include "map_volume.hpp"
@@ -437,6 +438,20 @@ int svoslam_workspace_component_buffers(const svoslam_workspace *ws, void *d_ptr
   if (!ws || !d_ptrs || !bytes) return SVOSLAM_ERR_INVALID_ARG;
   const svoslam::DeviceBuffer *slots[2] = {&ws->comp_bits, &ws->comp_ctl};
   for (int k = 0; k < 2; k++) { d_ptrs[k] = slots[k]->ptr; bytes[k] = slots[k]->bytes; }
+  return SVOSLAM_OK;
+}
+
+int svoslam_pool_nearest_field(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                               const int32_t dims[3], int32_t radius_cells, int32_t which, int32_t *d_dist2, uint64_t *d_cell,
+                               int32_t *d_node, uint32_t *d_color, void *stream) {
+  NEED_DEVICE();
+  return pool_nearest_field(ws, pool, max_depth, origin_cell, dims, radius_cells, which, d_dist2, d_cell, d_node, d_color, S(stream));
+}
+
+int svoslam_workspace_nearest_buffers(const svoslam_workspace *ws, void *d_ptrs[3], uint64_t bytes[3]) {
+  if (!ws || !d_ptrs || !bytes) return SVOSLAM_ERR_INVALID_ARG;
+  const svoslam::DeviceBuffer *slots[3] = {&ws->near_bits, &ws->near_dist, &ws->near_arg};
+  for (int k = 0; k < 3; k++) { d_ptrs[k] = slots[k]->ptr; bytes[k] = slots[k]->bytes; }
   return SVOSLAM_OK;
 }
 
