@@ -623,6 +623,49 @@ int svoslam_pool_nearest_field(svoslam_workspace *ws, const svoslam_pool *pool, 
 /* diagnostics: the device pointers and sizes in bytes of the workspace's three nearest-cell slots (the bit rows; the values; the
  * indices; NULL / 0 before the first call), as svoslam_workspace_field_buffers shows the distance field's.  Host only. */
 int svoslam_workspace_nearest_buffers(const svoslam_workspace *ws, void *d_ptrs[3], uint64_t bytes[3]);
+/* The visibility field of a map region (no reference counterpart; specification here and in DESIGN.md section 19): for every cell
+ * of a box of cells the viewpoints that have a free line of sight to it within a range -- what coverage ("which cells did these
+ * poses see"), next-best-view and sensor placement, line-of-sight pruning of a path from the reach field and visibility graphs
+ * between waypoints are made of.  Exact, in integers, symmetric, the same on every machine.
+ *   d, N, the occupied set, the region and the output order (x fastest, [nz, ny, nx]) are exactly those of
+ *     svoslam_pool_distance_field.  R = range_cells, 0..SVOSLAM_MAX_RADIUS_CELLS.
+ *   Viewpoints: d_views holds n_views triples (x, y, z) of int32 absolute cells at depth d, in device memory, as the reach field's
+ *     seeds are.  Viewpoint k COUNTS iff it lies in the root (0 <= v_a < N on every axis); it need not lie in the region, and
+ *     whether its own cell is occupied is ignored.  A viewpoint that does not count sees nothing.  Its bit keeps its position k:
+ *     bits are never renumbered.  Duplicates are allowed.  n_views = 0 is allowed, d_views may then be NULL, and the outputs are
+ *     all zero.
+ *   Sight: for cells v and q of the root let S(v, q) be the set of cells c, c != v and c != q, whose CLOSED cube [c, c + 1]^3 meets
+ *     the closed segment from v's centre to q's centre: the supercover of the segment without its two ends.  q is SEEN FROM v iff
+ *     |q - v|^2 <= R^2 and no cell of S(v, q) is occupied.  The rule is geometric, so sight is symmetric in v and q.  A segment
+ *     that touches an occupied cell only at an edge or a corner is blocked -- the conservative choice: no line of sight through a
+ *     crack of zero width; it deliberately differs from whatever tie rule svoslam_pool_cast_rays has.  An occupied q can be seen (a
+ *     sensor sees the surface cell); q == v is always seen; at R = 0 a viewpoint sees its own cell and nothing else.  Everything is
+ *     integers: in doubled coordinates the centres are odd and the cell faces even; with D = q - v the segment crosses axis a's
+ *     i-th face at parameter (2 i - 1) / (2 |D_a|); two crossings compare by cross-multiplication, (2 i - 1) |D_b| against
+ *     (2 j - 1) |D_a|, which stays below 2^25 at R = 4096; where two or three axes cross at the same parameter the segment passes
+ *     through an edge or a corner and all 4 or 8 cells around it belong to the supercover.
+ *   Outputs: each dims[0] * dims[1] * dims[2] values in device memory, indexed as svoslam_pool_distance_field's d_dist2.  Either may
+ *     be NULL; with a non-empty region not both.  d_mask (uint32): bit k is set iff viewpoint k counts and q is seen from it; it
+ *     needs n_views <= SVOSLAM_MAX_VIEWS_MASK.  d_count (int32): the number of viewpoint entries that count and see q, duplicates
+ *     counted each; any n_views.  Only the values are specified, not how they are computed.
+ *   Conventions: those of svoslam_pool_distance_field -- any pool (svoslam_pool_set_nodes words included); asynchronous on `stream`,
+ *     nothing is read back; pending asynchronous fusions are drained first; a pool whose deferred commit waits for its apply is
+ *     read in its old state.  The one intermediate, the occupancy of the region inflated by R and clipped to the root as bit rows,
+ *     lives in one grow-only workspace slot of its own, so a second call of the same size allocates nothing, and no other call's
+ *     slots are touched.
+ *   Errors: a zero entry of dims is SVOSLAM_OK and launches nothing, if the other arguments are valid.  SVOSLAM_ERR_INVALID_ARG:
+ *     those of svoslam_pool_distance_field, with range_cells for radius_cells; n_views < 0; NULL d_views with n_views > 0; d_mask
+ *     with n_views > SVOSLAM_MAX_VIEWS_MASK; with a non-empty region both outputs NULL.  SVOSLAM_ERR_POOL_LIMIT: more than 2^31 - 1
+ *     output cells or bit-row words, decided before anything is allocated or written.  SVOSLAM_ERR_OOM: the allocation failed;
+ *     nothing the call grew stays behind.
+ *   Not part of it: a field-of-view cone or sensor model per viewpoint, the first blocker of each line, sub-cell viewpoints. */
+#define SVOSLAM_MAX_VIEWS_MASK 32
+int svoslam_pool_visibility_field(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                                  const int32_t dims[3], int32_t range_cells, const int32_t *d_views, int32_t n_views,
+                                  uint32_t *d_mask /* may be NULL */, int32_t *d_count /* may be NULL */, void *stream);
+/* diagnostics: the device pointer and size in bytes of the workspace's visibility slot (the bit rows; NULL / 0 before the first
+ * call), as svoslam_workspace_field_buffers shows the distance field's.  Host only. */
+int svoslam_workspace_visibility_buffers(const svoslam_workspace *ws, void *d_ptrs[1], uint64_t bytes[1]);
 /* The library's own sort and scan, exposed for tests and tools (no reference counterpart).  Every map operation sorts Morton keys
  * with the stable LSD radix sort of csrc/radix_sort.hip and compacts with its exclusive scan; these two calls reach them with
  * arguments of the caller's choosing, where the map's calls choose the form and the digit width from n.  All arrays are in device
@@ -807,7 +850,7 @@ int svoslam_cone_trace_timing_read(float *h_ms_sum, int32_t *h_launches);
 #define SVOSLAM_STAGE_SURFACE_BFS 9    /* extract_surface_mesh: the occupied cells (incl. one readback per level) */
 #define SVOSLAM_STAGE_SURFACE_FACES 10 /* extract_surface_mesh: face masks + scan (incl. the count readback) | emission: two brackets per call, the host's allocations between them are outside */
 #define SVOSLAM_STAGE_SURFACE_WELD 11  /* extract_surface_mesh: corner sort + run heads + scan (incl. the count readback) | scatter: two brackets per call likewise */
-#define SVOSLAM_STAGE_QUERY 12         /* svoslam_pool_cast_rays / _query_points / _count_boxes / _nearest_occupied: the kernel, one bracket per call; svoslam_pool_distance_field: its four launches, one bracket per call; svoslam_pool_reach_field: the field's launches and every launch and readback of the relaxation, one bracket per call; svoslam_pool_label_components: the field's launches and its own, one bracket per call; svoslam_pool_nearest_field: its five launches, one bracket per call */
+#define SVOSLAM_STAGE_QUERY 12         /* svoslam_pool_cast_rays / _query_points / _count_boxes / _nearest_occupied: the kernel, one bracket per call; svoslam_pool_distance_field: its four launches, one bracket per call; svoslam_pool_reach_field: the field's launches and every launch and readback of the relaxation, one bracket per call; svoslam_pool_label_components: the field's launches and its own, one bracket per call; svoslam_pool_nearest_field: its five launches, one bracket per call; svoslam_pool_visibility_field: its two launches, one bracket per call */
 #define SVOSLAM_STAGE_COUNT 13
 int svoslam_stage_timing(uint32_t mask);
 int svoslam_stage_timing_read(int32_t stage, float *h_ms_sum, int32_t *h_pairs);

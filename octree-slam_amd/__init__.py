@@ -205,6 +205,9 @@ SIGNATURES = {
     "svoslam_pool_nearest_field": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _vp, _vp, _vp,
                                              _vp, _vp]),
     "svoslam_workspace_nearest_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "svoslam_pool_visibility_field": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _vp, _i32, _vp, _vp,
+                                                _vp]),
+    "svoslam_workspace_visibility_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
     "svoslam_sort_words": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "svoslam_exclusive_scan_u32": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp]),
     "svoslam_malloc": (C.c_int, [C.POINTER(_vp), C.c_size_t]),
@@ -394,6 +397,12 @@ class Workspace:
         ptrs, sizes = (_vp * 3)(), (C.c_uint64 * 3)()
         check(lib().svoslam_workspace_nearest_buffers(self._h, ptrs, sizes))
         return [(int(ptrs[k] or 0), int(sizes[k])) for k in range(3)]
+
+    def visibility_buffers(self):
+        """svoslam_workspace_visibility_buffers: [(device pointer, bytes)] of the visibility field's one slot (diagnostics)"""
+        ptrs, sizes = (_vp * 1)(), (C.c_uint64 * 1)()
+        check(lib().svoslam_workspace_visibility_buffers(self._h, ptrs, sizes))
+        return [(int(ptrs[0] or 0), int(sizes[0]))]
 
     def __del__(self):
         try:
@@ -931,6 +940,43 @@ def nearest_field(ws, pool, max_depth, origin, dims, radius_cells, which=0, want
     if as_tensor:
         return bufs
     return {name: b.cpu().numpy().view(fields[name][1]) if name in fields else b.cpu().numpy() for name, b in bufs.items()}
+
+
+MAX_VIEWS_MASK = 32                                                     # include/svoslam.h SVOSLAM_MAX_VIEWS_MASK
+
+
+def visibility_field(ws, pool, max_depth, origin, dims, range_cells, views, want=("mask",), as_tensor=False):
+    """svoslam_pool_visibility_field: for every cell of the region origin[3] .. origin + dims[3] (cells at max_depth, x y z) the
+    viewpoints that see it: `views` is [n, 3] absolute cells (an array, or an int32 cuda tensor); viewpoint k counts iff it lies in
+    the root, and sees cell q iff |q - k|^2 <= range_cells^2 and no occupied cell other than the two themselves touches the segment
+    between their centres (edges and corners block).  `want`: the subset of "mask" (uint32, bit k = viewpoint k sees the cell; at
+    most MAX_VIEWS_MASK viewpoints) and "count" (int32, the viewpoint entries that see the cell) to compute; the other is passed as
+    NULL.  -> a dict of [nz, ny, nx] arrays: numpy, or with as_tensor cuda tensors (mask int32: the same bits), in which case
+    nothing is synchronised."""
+    import torch
+    o, n = [int(v) for v in origin], [int(v) for v in dims]
+    if len(o) != 3 or len(n) != 3:
+        raise ValueError("origin and dims are three cells each (x, y, z)")
+    fields = {"mask": (torch.int32, np.uint32), "count": (torch.int32, np.int32)}
+    names = tuple(want)
+    for name in names:
+        if name not in fields:
+            raise KeyError("no output %r (have: %s)" % (name, ", ".join(fields)))
+    if isinstance(views, torch.Tensor):
+        if not views.is_cuda or views.dtype != torch.int32:
+            raise ValueError("a views tensor is int32 on the device")
+        t_views = views.reshape(-1, 3).contiguous()
+    else:
+        t_views = torch.from_numpy(np.ascontiguousarray(np.asarray(views, np.int32).reshape(-1, 3))).cuda()
+    count = int(t_views.shape[0])
+    shape = [max(v, 0) for v in reversed(n)]
+    bufs = {name: torch.empty(shape, dtype=fields[name][0], device="cuda") for name in names}
+    check(lib().svoslam_pool_visibility_field(ws._h, C.byref(pool._p), int(max_depth), (_i32 * 3)(*o), (_i32 * 3)(*n), int(range_cells),
+                                              _ptr(t_views) if count else None, count, *[_ptr(bufs.get(name)) for name in fields],
+                                              _stream()))
+    if as_tensor:
+        return bufs
+    return {name: b.cpu().numpy().view(fields[name][1]) for name, b in bufs.items()}
 
 
 def box_to_cells(max_depth, center, edge_length, box):

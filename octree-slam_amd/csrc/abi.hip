@@ -13,6 +13,7 @@
 #include "map_nearest.hpp"
 #include "map_query.hpp"
 #include "map_reach.hpp"
+#include "map_visibility.hpp"
 #include "map_volume.hpp"
 #include "mesh.hpp"
 #include "model_depth.hpp"
@@ -452,6 +453,20 @@ int svoslam_workspace_nearest_buffers(const svoslam_workspace *ws, void *d_ptrs[
   if (!ws || !d_ptrs || !bytes) return SVOSLAM_ERR_INVALID_ARG;
   const svoslam::DeviceBuffer *slots[3] = {&ws->near_bits, &ws->near_dist, &ws->near_arg};
   for (int k = 0; k < 3; k++) { d_ptrs[k] = slots[k]->ptr; bytes[k] = slots[k]->bytes; }
+  return SVOSLAM_OK;
+}
+
+int svoslam_pool_visibility_field(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                                  const int32_t dims[3], int32_t range_cells, const int32_t *d_views, int32_t n_views, uint32_t *d_mask,
+                                  int32_t *d_count, void *stream) {
+  NEED_DEVICE();
+  return pool_visibility_field(ws, pool, max_depth, origin_cell, dims, range_cells, d_views, n_views, d_mask, d_count, S(stream));
+}
+
+int svoslam_workspace_visibility_buffers(const svoslam_workspace *ws, void *d_ptrs[1], uint64_t bytes[1]) {
+  if (!ws || !d_ptrs || !bytes) return SVOSLAM_ERR_INVALID_ARG;
+  d_ptrs[0] = ws->vis_bits.ptr;
+  bytes[0] = ws->vis_bits.bytes;
   return SVOSLAM_OK;
 }
 
