@@ -666,6 +666,57 @@ int svoslam_pool_visibility_field(svoslam_workspace *ws, const svoslam_pool *poo
 /* diagnostics: the device pointer and size in bytes of the workspace's visibility slot (the bit rows; NULL / 0 before the first
  * call), as svoslam_workspace_field_buffers shows the distance field's.  Host only. */
 int svoslam_workspace_visibility_buffers(const svoslam_workspace *ws, void *d_ptrs[1], uint64_t bytes[1]);
+/* Scoring candidate poses against a distance field (no reference counterpart; specification here and in DESIGN.md section 20): for
+ * each of n_poses sensor-to-world matrices, move each of n sensor points by it, look the point's cell up in the field of a region
+ * and add the values up -- the inner loop of a likelihood-field or chamfer relocaliser ("where in this map was this depth frame
+ * taken?"), in one launch instead of a transform, a nearest-cell query and a readback per pose.  The sums are integers: exact,
+ * the same on every machine and in every order of summation.
+ *   The field: d_dist2 is dims[0] * dims[1] * dims[2] int32 in device memory, x fastest, exactly as svoslam_pool_distance_field
+ *     writes it for (max_depth, origin_cell, dims); svoslam_pool_nearest_field's dist2 serves as well.  A value >= 0 is a squared
+ *     distance in cells, a negative value means "none within the radius".  The call sees neither the pool nor the radius.  The
+ *     region has to lie inside the root, by svoslam_pool_distance_field's test.  d = max_depth, N = 2^d; the planes P_a(k) and the
+ *     count c_a(p) are svoslam_pool_cast_rays' (center, edge_length as there).
+ *   Points: d_points holds n triples of binary32 in the sensor frame, in device memory: what svoslam_generate_vertex_map writes,
+ *     at any pyramid level.  A point with a non-finite component is VOID and counts nowhere (the vertex map writes +inf for a
+ *     pixel without depth).
+ *   Poses: d_poses holds n_poses x 16 binary32 in device memory, each a sensor-to-world matrix in the layout of every trans[16] of
+ *     this header (column-major, m[4 * col + row]).
+ *   One (pose M, point p) pair, p not void:
+ *     1. w = M * (p, 1) in binary32, in the operation order of svoslam_transform_vertex_map: w_r = (m[r] * p.x + m[4 + r] * p.y) +
+ *        (m[8 + r] * p.z + m[12 + r] * 1.0f), no fused multiply-add.
+ *     2. the pair is OUTSIDE if a component of w is not finite;
+ *     3. OUTSIDE if !(P_a(0) <= w_a <= P_a(N)) on any axis: the root test of svoslam_pool_nearest_occupied;
+ *     4. otherwise q_a = c_a(w_a), the non-strict count: the cell svoslam_pool_nearest_occupied gives the point;
+ *     5. OUTSIDE if q is not in the region;
+ *     6. otherwise v = d_dist2[q]: the pair is FAR if v < 0 and NEAR if v >= 0.
+ *   Per pose: cost = the sum of v over the NEAR pairs + miss_cost * (FAR + OUTSIDE), in int64; near, far, outside = the three
+ *     counts, near + far + outside = the number of non-void points.  The natural miss_cost is R^2 + 1 of the field; any value in
+ *     0..2^30 is allowed.
+ *   Best: d_best is 2 x int64 = (cost, index) of the pose with the smallest cost among those with near >= min_near, among equal
+ *     costs the lowest index; (-1, -1) if no pose qualifies, n_poses == 0 included.
+ *   Outputs: d_cost (n_poses int64), d_near, d_far, d_outside (n_poses int32 each), d_best, all in device memory.  Each may be
+ *     NULL; with n_poses > 0 not all five.  All are written asynchronously on `stream`; nothing is read back.  Only the values are
+ *     specified, not how they are computed.
+ *   Workspace: intermediates (a record per pose, when d_best is wanted or the points of one pose are split over workgroups) live
+ *     in one grow-only workspace slot of their own: a second call of the same size allocates nothing, no other call's slot is
+ *     touched.
+ *   Errors: n == 0, or no non-void point, is valid: every pose has cost 0 and counts 0.  n_poses == 0 is SVOSLAM_OK and launches
+ *     at most the write of d_best.  A zero entry of dims is valid: every non-void pair is OUTSIDE.  SVOSLAM_ERR_INVALID_ARG: ws,
+ *     center, origin_cell or dims NULL; max_depth outside 1..SVOSLAM_MAX_DEPTH; !(edge_length > 0); a negative entry of dims; a
+ *     region not inside the root; n < 0; n_poses < 0; miss_cost outside 0..2^30; min_near < 0; NULL d_points with n > 0; NULL
+ *     d_poses with n_poses > 0; NULL d_dist2 with a non-empty region and n > 0 and n_poses > 0; all outputs NULL with n_poses > 0.
+ *     SVOSLAM_ERR_POOL_LIMIT: more than 2^31 - 1 region cells.  SVOSLAM_ERR_OOM: the allocation failed; nothing the call grew stays
+ *     behind.  Nothing is launched on an error.
+ *   Not part of it: setting a tracker's pose from the answer; normals or colour in the score; a sensor model for free space;
+ *     sub-cell interpolation of the field. */
+#define SVOSLAM_MAX_MISS_COST (1 << 30)
+int svoslam_score_poses(svoslam_workspace *ws, const int32_t *d_dist2, int32_t max_depth, const float center[3], float edge_length,
+                        const int32_t origin_cell[3], const int32_t dims[3], const float *d_points, int32_t n,
+                        const float *d_poses, int32_t n_poses, int32_t miss_cost, int32_t min_near,
+                        int64_t *d_cost, int32_t *d_near, int32_t *d_far, int32_t *d_outside, int64_t *d_best, void *stream);
+/* diagnostics: the device pointer and size in bytes of the workspace's scoring slot (the per-pose records; NULL / 0 before the
+ * first call that needs them), as svoslam_workspace_field_buffers shows the distance field's.  Host only. */
+int svoslam_workspace_score_buffers(const svoslam_workspace *ws, void *d_ptrs[1], uint64_t bytes[1]);
 /* The library's own sort and scan, exposed for tests and tools (no reference counterpart).  Every map operation sorts Morton keys
  * with the stable LSD radix sort of csrc/radix_sort.hip and compacts with its exclusive scan; these two calls reach them with
  * arguments of the caller's choosing, where the map's calls choose the form and the digit width from n.  All arrays are in device
@@ -850,7 +901,7 @@ int svoslam_cone_trace_timing_read(float *h_ms_sum, int32_t *h_launches);
 #define SVOSLAM_STAGE_SURFACE_BFS 9    /* extract_surface_mesh: the occupied cells (incl. one readback per level) */
 #define SVOSLAM_STAGE_SURFACE_FACES 10 /* extract_surface_mesh: face masks + scan (incl. the count readback) | emission: two brackets per call, the host's allocations between them are outside */
 #define SVOSLAM_STAGE_SURFACE_WELD 11  /* extract_surface_mesh: corner sort + run heads + scan (incl. the count readback) | scatter: two brackets per call likewise */
-#define SVOSLAM_STAGE_QUERY 12         /* svoslam_pool_cast_rays / _query_points / _count_boxes / _nearest_occupied: the kernel, one bracket per call; svoslam_pool_distance_field: its four launches, one bracket per call; svoslam_pool_reach_field: the field's launches and every launch and readback of the relaxation, one bracket per call; svoslam_pool_label_components: the field's launches and its own, one bracket per call; svoslam_pool_nearest_field: its five launches, one bracket per call; svoslam_pool_visibility_field: its two launches, one bracket per call */
+#define SVOSLAM_STAGE_QUERY 12         /* svoslam_pool_cast_rays / _query_points / _count_boxes / _nearest_occupied: the kernel, one bracket per call; svoslam_pool_distance_field: its four launches, one bracket per call; svoslam_pool_reach_field: the field's launches and every launch and readback of the relaxation, one bracket per call; svoslam_pool_label_components: the field's launches and its own, one bracket per call; svoslam_pool_nearest_field: its five launches, one bracket per call; svoslam_pool_visibility_field: its two launches, one bracket per call; svoslam_score_poses: its one to three launches, one bracket per call */
 #define SVOSLAM_STAGE_COUNT 13
 int svoslam_stage_timing(uint32_t mask);
 int svoslam_stage_timing_read(int32_t stage, float *h_ms_sum, int32_t *h_pairs);

@@ -13,6 +13,7 @@
 #include "map_nearest.hpp"
 #include "map_query.hpp"
 #include "map_reach.hpp"
+#include "map_score.hpp"
 #include "map_visibility.hpp"
 #include "map_volume.hpp"
 #include "mesh.hpp"
@@ -467,6 +468,22 @@ int svoslam_workspace_visibility_buffers(const svoslam_workspace *ws, void *d_pt
   if (!ws || !d_ptrs || !bytes) return SVOSLAM_ERR_INVALID_ARG;
   d_ptrs[0] = ws->vis_bits.ptr;
   bytes[0] = ws->vis_bits.bytes;
+  return SVOSLAM_OK;
+}
+
+int svoslam_score_poses(svoslam_workspace *ws, const int32_t *d_dist2, int32_t max_depth, const float center[3], float edge_length,
+                        const int32_t origin_cell[3], const int32_t dims[3], const float *d_points, int32_t n, const float *d_poses,
+                        int32_t n_poses, int32_t miss_cost, int32_t min_near, int64_t *d_cost, int32_t *d_near, int32_t *d_far,
+                        int32_t *d_outside, int64_t *d_best, void *stream) {
+  NEED_DEVICE();
+  return score_poses(ws, d_dist2, max_depth, center, edge_length, origin_cell, dims, d_points, n, d_poses, n_poses, miss_cost, min_near,
+                     d_cost, d_near, d_far, d_outside, d_best, S(stream));
+}
+
+int svoslam_workspace_score_buffers(const svoslam_workspace *ws, void *d_ptrs[1], uint64_t bytes[1]) {
+  if (!ws || !d_ptrs || !bytes) return SVOSLAM_ERR_INVALID_ARG;
+  d_ptrs[0] = ws->score_rec.ptr;
+  bytes[0] = ws->score_rec.bytes;
   return SVOSLAM_OK;
 }
 
