@@ -131,6 +131,27 @@ int svoslam_pool_touch(svoslam_pool *pool);
  * deeper than any shape), -1 the field could not be allocated -- the pool is marched through the tree (correct, slower);
  * *brick_shift = the shape (0: depth <= 12, 1: depth 13 / 14, -1: none).  Any of the pointers may be NULL. */
 int svoslam_pool_march_accel(const svoslam_pool *pool, int32_t *has_grid, int32_t *brick_state, int32_t *brick_shift);
+/* A read-only view of the tables the march of this pool reads, and of their upkeep state (tests and diagnostics: DESIGN.md
+ * section 4, tests/accel_ref.py states the rules the tables follow).  Host state and device ADDRESSES only: nothing is launched,
+ * refreshed, allocated or invalidated, so looking does not change what is looked at; the caller synchronises the device before
+ * it reads through the addresses.  A pool that is not registered gives all zeros. */
+typedef struct svoslam_accel_view {
+  void *grid;          /* uint2[2^24] level-8 grid, the pyramid of levels 1..7 behind it at entry 2^24; NULL before the first render */
+  void *bricks;        /* uint16 brick field (16 GiB, addressed by window cell); NULL: none */
+  void *brick_touched; /* uint32[8192]: one bit per 64 KB group of the field that holds anything */
+  void *dirty[2];      /* the two dirty states (uint32 words, laid out as the offsets below say); NULL before the first commit / render */
+  int32_t valid, bricks_valid, brick_shift, mip_consistent, max_depth, deferred_pending;  /* as the host sees them */
+  int32_t bricks_failed;
+  uint32_t epoch;            /* of the latest deferred commit: while one is pending it marks dirty[epoch & 1] */
+  uint32_t node0_served;     /* refreshes so far; the latest wrote node 0's word to dirty[0][node0_offset + ((node0_served - 1) & 1)] */
+  uint32_t brick_served[2];  /* per state: refreshes that served its rings; the latest wrote mark [(brick_served - 1) & 1] */
+  /* word offsets into a dirty state: bitmap of the level-5 blocks [dirty_words], list of marked blocks, its count, node 0's two
+   * words, the stale-brick ring (count, two marks behind it, entries [brick_list_cap]), one bit per brick "in this ring"
+   * [brick_bits_words], the sibling ring (count, two marks, entries [sib_list_cap]) */
+  int32_t dirty_words, list_offset, count_offset, node0_offset, brick_count_offset, brick_list_offset, brick_list_cap,
+      brick_bits_offset, brick_bits_words, sib_count_offset, sib_list_offset, sib_list_cap, state_words;
+} svoslam_accel_view;
+int svoslam_pool_accel_view(const svoslam_pool *pool, svoslam_accel_view *view);
 /* Replaces the pool's contents by num_nodes host nodes (2 words each, reference format; child pointers validated) and
  * resets all size bookkeeping incl. the device-resident size the asynchronous fusion allocates from.  Blocking. */
 int svoslam_pool_set_nodes(svoslam_pool *pool, const uint32_t *h_words, int32_t num_nodes, void *stream);

@@ -73,6 +73,17 @@ class CompactStats(C.Structure):
                 ("levels", C.c_int32), ("tiles_dropped", C.c_int32)]
 
 
+class AccelView(C.Structure):
+    """include/svoslam.h svoslam_accel_view"""
+    _fields_ = ([("grid", C.c_void_p), ("bricks", C.c_void_p), ("brick_touched", C.c_void_p), ("dirty", C.c_void_p * 2)] +
+                [(n, C.c_int32) for n in ("valid", "bricks_valid", "brick_shift", "mip_consistent", "max_depth", "deferred_pending",
+                                          "bricks_failed")] +
+                [("epoch", C.c_uint32), ("node0_served", C.c_uint32), ("brick_served", C.c_uint32 * 2)] +
+                [(n, C.c_int32) for n in ("dirty_words", "list_offset", "count_offset", "node0_offset", "brick_count_offset",
+                                          "brick_list_offset", "brick_list_cap", "brick_bits_offset", "brick_bits_words",
+                                          "sib_count_offset", "sib_list_offset", "sib_list_cap", "state_words")])
+
+
 class SurfaceStats(C.Structure):
     _fields_ = [("cells", C.c_int32), ("faces", C.c_int32), ("vertices", C.c_int32)]
 
@@ -99,6 +110,7 @@ SIGNATURES = {
     "svoslam_pool_save": (C.c_int, [C.POINTER(_PoolStruct), C.c_char_p, _fp, _f32, _i32, _vp]),
     "svoslam_pool_touch": (C.c_int, [C.POINTER(_PoolStruct)]),
     "svoslam_pool_march_accel": (C.c_int, [C.POINTER(_PoolStruct), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "svoslam_pool_accel_view": (C.c_int, [C.POINTER(_PoolStruct), C.POINTER(AccelView)]),
     "svoslam_pool_set_nodes": (C.c_int, [C.POINTER(_PoolStruct), C.POINTER(C.c_uint32), _i32, _vp]),
     "svoslam_pool_evict_subtree": (C.c_int, [C.POINTER(_PoolStruct), C.POINTER(C.c_uint8), _i32, C.c_char_p, _vp]),
     "svoslam_pool_restore_subtree": (C.c_int, [C.POINTER(_PoolStruct), C.c_char_p, _vp]),
@@ -507,6 +519,45 @@ class Pool:
         g, b, sh = C.c_int32(0), C.c_int32(0), C.c_int32(-1)
         check(lib().svoslam_pool_march_accel(C.byref(self._p), C.byref(g), C.byref(b), C.byref(sh)))
         return {"grid": bool(g.value), "bricks": int(b.value), "brick_shift": int(sh.value)}
+
+    def accel_view(self):
+        """svoslam_pool_accel_view: the march's tables and their upkeep state as the library holds them right now, as a dict of
+        device addresses (0: none), host flags and word offsets into a dirty state.  Launches nothing and changes nothing."""
+        v = AccelView()
+        check(lib().svoslam_pool_accel_view(C.byref(self._p), C.byref(v)))
+        out = {n: getattr(v, n) for n, _ in AccelView._fields_ if n not in ("dirty", "brick_served")}
+        for n in ("grid", "bricks", "brick_touched"):
+            out[n] = int(out[n] or 0)
+        for n in ("valid", "bricks_valid", "mip_consistent", "deferred_pending", "bricks_failed"):
+            out[n] = bool(out[n])
+        out["dirty"] = [int(v.dirty[k] or 0) for k in range(2)]
+        out["brick_served"] = [int(v.brick_served[k]) for k in range(2)]
+        out["bricks_in_use"] = bool(out["bricks"]) and out["bricks_valid"] and out["brick_shift"] >= 0
+        return out
+
+    def accel_grid(self, view=None):
+        """the level-8 grid and the pyramid behind it as host words: (uint32 [2^24, 2], uint32 [pyramid entries, 2]); None
+        before the first render"""
+        v = view or self.accel_view()
+        if not v["grid"]:
+            return None
+        n8, npyr = 1 << 24, ((1 << 24) - 8) // 7
+        both = copy_from_device(v["grid"], (n8 + npyr, 2), np.uint32)
+        return both[:n8], both[n8:]
+
+    def accel_brick_group(self, group, view=None):
+        """one 64 KB group of the brick field (8^3 bricks of 64 entries) as host uint16 [32768]"""
+        v = view or self.accel_view()
+        if not v["bricks"] or not 0 <= int(group) < (1 << 18):
+            raise SvoslamError("no brick field, or no such group")
+        return copy_from_device(v["bricks"] + int(group) * 65536, (32768,), np.uint16)
+
+    def accel_dirty_words(self, state, offset, count, view=None):
+        """`count` words of dirty state `state` from word `offset` on (uint32)"""
+        v = view or self.accel_view()
+        if not v["dirty"][state] or offset < 0 or offset + count > v["state_words"]:
+            raise SvoslamError("no such dirty state, or words outside it")
+        return copy_from_device(v["dirty"][state] + 4 * int(offset), (int(count),), np.uint32)
 
     def expand(self, center, edge_length, toward):
         """doubles the root cube towards `toward` (re-rooting); returns the new (center, edge_length)"""

@@ -140,6 +140,11 @@ int svoslam_pool_march_accel(const svoslam_pool *pool, int32_t *has_grid, int32_
   if (brick_shift) *brick_shift = pa && pa->bricks ? pa->brick_shift : -1;
   return SVOSLAM_OK;
 }
+int svoslam_pool_accel_view(const svoslam_pool *pool, svoslam_accel_view *view) {
+  if (!pool || !view) return SVOSLAM_ERR_INVALID_ARG;
+  pool_accel_view(pool->d_data, view);  // (host state and addresses: no device call)
+  return SVOSLAM_OK;
+}
 int svoslam_pool_sync(svoslam_pool *pool, void *stream) {
   NEED_DEVICE();
   return pool_sync(pool, S(stream));

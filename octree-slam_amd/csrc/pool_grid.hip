@@ -173,6 +173,36 @@ std::shared_ptr<PoolAccel> pool_accel_find(const uint32_t *d_data) {
   return it == g_accel.end() ? nullptr : it->second;
 }
 
+void pool_accel_view(const uint32_t *d_data, svoslam_accel_view *view) {
+  *view = svoslam_accel_view{};
+  view->brick_shift = -1;
+  view->dirty_words = kPoolGridDirtyWords; view->list_offset = kPoolGridListOffset; view->count_offset = kPoolGridCountOffset;
+  view->node0_offset = kPoolGridNode0Offset;
+  view->brick_count_offset = kBrickCountOffset; view->brick_list_offset = kBrickListOffset; view->brick_list_cap = kBrickListCap;
+  view->brick_bits_offset = kBrickBitsOffset; view->brick_bits_words = kBrickBitsWords;
+  view->sib_count_offset = kSibCountOffset; view->sib_list_offset = kSibListOffset; view->sib_list_cap = kSibListCap;
+  view->state_words = kPoolGridStateWords;
+  if (!d_data) return;
+  std::lock_guard<std::mutex> lock(g_mu);
+  auto it = g_accel.find(d_data);
+  if (it == g_accel.end()) return;
+  const PoolAccel *pa = it->second.get();
+  view->grid = pa->grid.ptr;
+  view->bricks = pa->bricks;
+  view->brick_touched = pa->d_brick_touched;
+  view->dirty[0] = pa->d_dirty[0]; view->dirty[1] = pa->d_dirty[1];
+  view->valid = pa->valid ? 1 : 0;
+  view->bricks_valid = pa->bricks_valid ? 1 : 0;
+  view->brick_shift = pa->bricks ? pa->brick_shift : -1;
+  view->mip_consistent = pa->mip_consistent ? 1 : 0;
+  view->max_depth = pa->max_depth;
+  view->deferred_pending = pa->deferred_pending ? 1 : 0;
+  view->bricks_failed = pa->bricks_failed ? 1 : 0;
+  view->epoch = pa->epoch;
+  view->node0_served = pa->node0_served;
+  view->brick_served[0] = pa->brick_served[0]; view->brick_served[1] = pa->brick_served[1];
+}
+
 // outcome of the reference's walk over levels 1..G on the path of cell (xi, yi, zi) (cone_tracing_kernels.cu:76-105):
 //   all G nodes have children:  x = flag | tile index of the level-G node's children, y = its colour word
 //   first childless node at level st (1..G): x = st, y = that node's colour word

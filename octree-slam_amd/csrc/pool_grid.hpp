@@ -109,6 +109,9 @@ uint32_t *pool_accel_dirty_bitmap(svoslam_pool *pool, int parity, int commit_dep
 std::shared_ptr<PoolAccel> pool_accel_find(const uint32_t *d_data);  // the registered pool whose nodes start at d_data, or null;
 // the caller holds the entry for the duration of its enqueue (a pool_free / growth on another host thread cannot pull it away)
 void pool_accel_forget_stream(hipStream_t stream);       // the stream is about to be destroyed
+// what the entry of the pool at d_data holds, under the registry's mutex (svoslam_pool_accel_view): reads only -- it refreshes,
+// allocates and invalidates nothing; all zeros for memory that is not a registered pool
+void pool_accel_view(const uint32_t *d_data, svoslam_accel_view *view);
 
 // shadow words of the pool (allocated and zeroed on first use / growth), the epoch of the commit that starts now
 int pool_shadow_begin(svoslam_pool *pool, hipStream_t stream, unsigned long long **d_shadow, uint32_t *epoch);
