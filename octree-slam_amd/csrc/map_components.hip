@@ -6,15 +6,14 @@
 // existing host function and its kernels, into d_labels itself; everything after it is integers on the region: a union-find whose
 // parent array is d_labels.
 //
-//   components_pack_kernel     one wavefront per 64 consecutive x of a row: the ballot of (dist2 == -1) != solid is the row word of
-//                              S (reach_pack_kernel's layout), written by lane 0 with one vector store.
+//   the pack                   map_region.hip's region_pack_kernel<false>: (dist2 == -1) != solid as the row words of S, for the
+//                              region itself.
 //   components_tile_kernel     one workgroup of 256 per tile of 64 x 8 x 8 cells.  The 64 row words and one int32 per cell live in
 //                              LDS (16 KB + 512 B, no halo; a row is 64 consecutive dwords, so every access is conflict-free).  A
 //                              cell of S starts with its own output index, every other cell with "none".  One pass = three sweeps
-//                              with a barrier between them: x, a wavefront per row, the minimum over the run of set bits by doubling
-//                              (k = 1 .. 32 through __shfl_up / __shfl_down; a step of k is taken only where the row word has all
-//                              k + 1 bits set); y and z, a lane per column, a serial minimum up and down the 8 cells, restarted at
-//                              every cell that is not in S.  Passes repeat until one lowers nothing (a workgroup-wide OR): every
+//                              with a barrier between them (map_sweeps.hpp, with a step of 0): x, a wavefront per row, sweep_row's
+//                              minimum over the run of set bits; y and z, a lane per column, sweep_column's serial minimum up and
+//                              down the 8 cells.  Passes repeat until one lowers nothing (a workgroup-wide OR): every
 //                              pass lowers a value or is the last.  Each cell of S then stores its tile-local minimum: that is the
 //                              parent array, parent[q] <= q, and a tile-local root points at itself.  Other cells store -1.
 //   components_merge_kernel    one lane per cell on the low side of a tile face (x = 63 mod 64, y = 7 mod 8, z = 7 mod 8) that has a
@@ -49,8 +48,7 @@
 // arrays indexed at run time.  Every device loop ends by its own data: a find's indices fall strictly, a union continues only
 // with smaller indices, a tile pass lowers a value or is the last.  The call is asynchronous unless stats are asked for.
 // Resource report (hipcc -Rpass-analysis=kernel-resource-usage, gfx950), scratch 0 bytes for every kernel:
-//   components_pack_kernel     14 VGPRs, 25 SGPRs, no LDS, occupancy 8
-//   components_tile_kernel     58 VGPRs, 71 SGPRs, 17152 bytes of static LDS (9 workgroups per CU of 160 KB), occupancy 8
+//   components_tile_kernel     58 VGPRs, 69 SGPRs, 17152 bytes of static LDS (9 workgroups per CU of 160 KB), occupancy 8
 //   components_merge_kernel    15 VGPRs, 40 SGPRs, no LDS, occupancy 8
 //   components_flatten_kernel  10 VGPRs, 18 SGPRs, no LDS, occupancy 8
 //   components_count_kernel    16 VGPRs, 30 SGPRs, no LDS, occupancy 8
@@ -59,8 +57,9 @@
 
 #include "map_components.hpp"
 #include "map_field.hpp"
+#include "map_region.hpp"
+#include "map_sweeps.hpp"
 #include "stage_timing.hpp"
-#include "workspace.hpp"
 
 namespace svoslam {
 
@@ -87,17 +86,6 @@ __device__ inline int find_root(const int32_t *parent, int x) {  // the indices 
     if (p == x) return x;
     x = p;
   }
-}
-
-__global__ __launch_bounds__(256) void components_pack_kernel(const int32_t *__restrict__ dist2, int nx, int wpr, long long words, int solid,
-                                                              unsigned long long *__restrict__ bits) {
-  const long long word = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);  // one wavefront per row word
-  if (word >= words) return;
-  const int lane = threadIdx.x & 63;
-  const int x = (int)(word % wpr) * 64 + lane;
-  const bool in = x < nx;
-  const unsigned long long row_word = __ballot(in && (dist2[(word / wpr) * nx + x] == -1) != (solid != 0));
-  if (lane == 0) bits[word] = row_word;
 }
 
 __global__ __launch_bounds__(256) void components_tile_kernel(int32_t *__restrict__ labels, const unsigned long long *__restrict__ bits, int nx,
@@ -130,78 +118,22 @@ __global__ __launch_bounds__(256) void components_tile_kernel(int32_t *__restric
       if (tw == 0ull) continue;  // the same for the whole wavefront
       const int at = r * kTileX + lane;
       const int before = s[at];
-      int v = before;
-#pragma unroll
-      for (int k = 1; k < 64; k *= 2) {  // from below: cells lane - k .. lane all in S
-        const int u = __shfl_up(v, k);
-        const unsigned long long run = ((2ull << k) - 1ull) << (lane >= k ? lane - k : 0);
-        if (lane >= k && (tw & run) == run) v = min(v, u);
-      }
-#pragma unroll
-      for (int k = 1; k < 64; k *= 2) {  // from above: cells lane .. lane + k
-        const int u = __shfl_down(v, k);
-        const unsigned long long run = ((2ull << k) - 1ull) << lane;
-        if (lane + k < 64 && (tw & run) == run) v = min(v, u);
-      }
+      const int v = sweep_row<0>(before, tw, lane);
       if (v < before) { s[at] = v; changed = 1; }
     }
     __syncthreads();
     // y: a lane per (x, z) column
     for (int z = w; z < kTileZ; z += 4) {
-      const int col = z * kTileY * kTileX + lane;
-      int prev = kNone;
-#pragma unroll
-      for (int y = 0; y < kTileY; y++) {
-        const int at = col + y * kTileX;
-        if ((row_bits[z * 8 + y] >> lane) & 1ull) {
-          const int v = s[at];
-          prev = min(v, prev);
-          if (prev < v) { s[at] = prev; changed = 1; }
-        } else {
-          prev = kNone;
-        }
-      }
-      prev = kNone;
-#pragma unroll
-      for (int y = kTileY - 1; y >= 0; y--) {
-        const int at = col + y * kTileX;
-        if ((row_bits[z * 8 + y] >> lane) & 1ull) {
-          const int v = s[at];
-          prev = min(v, prev);
-          if (prev < v) { s[at] = prev; changed = 1; }
-        } else {
-          prev = kNone;
-        }
-      }
+      int32_t *col = s + z * kTileY * kTileX + lane;
+      changed |= sweep_column<0, kNone, kTileX, 1, true>(col, row_bits + z * 8, lane, kNone);
+      changed |= sweep_column<0, kNone, kTileX, 1, false>(col, row_bits + z * 8, lane, kNone);
     }
     __syncthreads();
     // z: a lane per (x, y) column
     for (int y = w; y < kTileY; y += 4) {
-      const int col = y * kTileX + lane;
-      int prev = kNone;
-#pragma unroll
-      for (int z = 0; z < kTileZ; z++) {
-        const int at = col + z * kTileY * kTileX;
-        if ((row_bits[z * 8 + y] >> lane) & 1ull) {
-          const int v = s[at];
-          prev = min(v, prev);
-          if (prev < v) { s[at] = prev; changed = 1; }
-        } else {
-          prev = kNone;
-        }
-      }
-      prev = kNone;
-#pragma unroll
-      for (int z = kTileZ - 1; z >= 0; z--) {
-        const int at = col + z * kTileY * kTileX;
-        if ((row_bits[z * 8 + y] >> lane) & 1ull) {
-          const int v = s[at];
-          prev = min(v, prev);
-          if (prev < v) { s[at] = prev; changed = 1; }
-        } else {
-          prev = kNone;
-        }
-      }
+      int32_t *col = s + y * kTileX + lane;
+      changed |= sweep_column<0, kNone, kTileY * kTileX, 8, true>(col, row_bits + y, lane, kNone);
+      changed |= sweep_column<0, kNone, kTileY * kTileX, 8, false>(col, row_bits + y, lane, kNone);
     }
     passes++;
     again = __syncthreads_or(changed);  // also the barrier in front of the next pass's x sweep
@@ -344,18 +276,13 @@ int pool_label_components(svoslam_workspace *ws, const svoslam_pool *pool, int d
                           int32_t r, int32_t which, int32_t *d_labels, int32_t *d_sizes, svoslam_component_stats *stats,
                           hipStream_t stream) {
   if (stats) stats->components = stats->largest = stats->tile_passes = stats->unions = 0;
-  if (!ws || !origin || !dims || depth < 1 || depth > SVOSLAM_MAX_DEPTH) return SVOSLAM_ERR_INVALID_ARG;
-  if (r < 0 || r > SVOSLAM_MAX_RADIUS_CELLS || (which != SVOSLAM_COMPONENTS_FREE && which != SVOSLAM_COMPONENTS_SOLID))
+  if (!ws || r < 0 || r > SVOSLAM_MAX_RADIUS_CELLS || (which != SVOSLAM_COMPONENTS_FREE && which != SVOSLAM_COMPONENTS_SOLID))
     return SVOSLAM_ERR_INVALID_ARG;
-  bool nothing = false;
-  for (int a = 0; a < 3; a++) {
-    if (dims[a] < 0 || origin[a] < 0 || (long long)origin[a] + dims[a] > (1ll << depth)) return SVOSLAM_ERR_INVALID_ARG;
-    nothing = nothing || dims[a] == 0;
-  }
-  if (nothing) return SVOSLAM_OK;
+  RegionPlan own;  // the region itself: its row words are <= the field's own, within its limits
+  SVO_TRY(plan_region(depth, origin, dims, 0, &own));
+  if (own.nothing) return SVOSLAM_OK;
   if (!pool || !pool->d_data || !d_labels) return SVOSLAM_ERR_INVALID_ARG;  // argument errors come before the limits
-  const long long nx = dims[0], ny = dims[1], nz = dims[2], n = nx * ny * nz;  // every side is <= 2^16: no overflow
-  const long long wpr = (nx + 63) / 64, words = wpr * ny * nz;  // <= the field's own row words: within its limits
+  const long long nx = own.nx, ny = own.ny, nz = own.nz, n = own.n_out, wpr = own.wpr, words = own.words;
   const long long tiles_x = wpr, tiles_y = (ny + kTileY - 1) / kTileY, tiles_z = (nz + kTileZ - 1) / kTileZ;
   const long long tiles = tiles_x * tiles_y * tiles_z;
   // a launch takes at most 2^32 - 1 work-items: decided here, before anything is allocated or written
@@ -366,24 +293,16 @@ int pool_label_components(svoslam_workspace *ws, const svoslam_pool *pool, int d
   }
   // the set, as the field's -1, in d_labels: the rest of the argument checks, the field's limits (decided before anything is
   // allocated), the drain of pending fusions and the field's own slots are pool_distance_field's
-  svoslam::DeviceBuffer *slots[5] = {&ws->field_bits, &ws->field_a, &ws->field_b, &ws->comp_bits, &ws->comp_ctl};
-  size_t had[5];
-  for (int k = 0; k < 5; k++) had[k] = slots[k]->bytes;
+  SlotRollback grown(ws, &ws->comp_bits, &ws->comp_ctl);
   AdoptedBracket bracket(stream);
   SVO_TRY(pool_distance_field(ws, pool, depth, origin, dims, r, d_labels, nullptr, stream, &bracket.token));
   int rc = ws->comp_bits.reserve((size_t)words * 8);
   if (rc == SVOSLAM_OK) rc = ws->comp_ctl.reserve(kControlBytes);
-  if (rc != SVOSLAM_OK) {  // the slots this call grew do not stay behind; the field's launches have finished before theirs go
-    (void)hipStreamSynchronize(stream);
-    for (int k = 0; k < 5; k++)
-      if (slots[k]->bytes != had[k]) slots[k]->release();
-    return rc;
-  }
+  if (rc != SVOSLAM_OK) return grown.undo(rc, stream);
   unsigned long long *bits = ws->comp_bits.as<unsigned long long>();
   ComponentControl *ctl = ws->comp_ctl.as<ComponentControl>();
   SVO_HIP(hipMemsetAsync(ctl, 0, kControlBytes, stream));
-  components_pack_kernel<<<cdiv(words, 4), 256, 0, stream>>>(d_labels, (int)nx, (int)wpr, words, which, bits);
-  SVO_LAUNCH_CHECK();
+  SVO_TRY(region_pack(own, d_labels, which == SVOSLAM_COMPONENTS_SOLID, nullptr, bits, stream));
   components_tile_kernel<<<(unsigned)tiles, 256, 0, stream>>>(d_labels, bits, (int)nx, (int)ny, (int)nz, (int)wpr, (int)tiles_x, (int)tiles_y,
                                                               ctl);
   SVO_LAUNCH_CHECK();

@@ -1,4 +1,4 @@
-// map_descend.hpp -- what the volume queries (map_volume.hip) and the distance field's raster (map_field.hip) share: the Morton
+// map_descend.hpp -- what the volume queries (map_volume.hip) and the region fields' raster (map_region.hip) share: the Morton
 // code of a cell (x lowest: the pool's octant order) and one descent from the root along a cell's path
 #pragma once
 #include "common.hpp"

@@ -5,18 +5,16 @@
 // clearance_cells writes -1 there, so the field is computed first, by the existing host function and its kernels, into d_steps
 // itself; everything after it is integers on the region.
 //
-//   reach_pack_kernel   one wavefront per 64 consecutive x of a row: the ballot of dist2 == -1 is the row word of the traversable
-//                       bits (field_raster_kernel's layout, for the region itself), written by lane 0 with one vector store; every
-//                       lane then overwrites its own dist2 with "none" (2^30): d_steps becomes the working array in place, and no
-//                       slot of the size of the output is needed.
+//   the pack            map_region.hip's region_pack_kernel<true>: the row words of the traversable bits (dist2 == -1), for the
+//                       region itself; every lane then overwrites its own dist2 with "none" (2^30): d_steps becomes the working
+//                       array in place, and no slot of the size of the output is needed.
 //   reach_seed_kernel   one lane per seed entry: a seed in the region whose bit is set writes 0, is counted, and marks its tile.
 //   reach_relax_kernel  one workgroup of 256 per tile of 64 x 8 x 8 cells, launched over all tiles; a tile whose flag of this
 //                       round is clear leaves at once.  The tile's steps with a one-cell halo (10 x 10 rows of 66 dwords, 26400
-//                       bytes) and its 64 row words are staged in LDS.  One pass = three sweeps, each exact along its axis:
-//                         x  a wavefront per row, a lane per cell: min-plus prefix scans up and down the row by doubling (k = 1,
-//                            2, .. 32 through __shfl_up / __shfl_down); a step of k is taken only where the row word has all of
-//                            the k + 1 bits from source to target set, so nothing passes through a blocked cell;
-//                         y  a lane per (x, z) column, serial up and down the 8 cells from the halo, x across the lanes;
+//                       bytes) and its 64 row words are staged in LDS.  One pass = three sweeps, each exact along its axis
+//                       (map_sweeps.hpp, with a step of 1 per move):
+//                         x  a wavefront per row, a lane per cell: sweep_row, after the two halo cells of the row;
+//                         y  a lane per (x, z) column: sweep_column up and down the 8 cells from the halo, x across the lanes;
 //                         z  the same per (x, y) column.
 //                       In every sweep a lane reads and writes only cells it owns in that sweep (and reads the halo, which nobody
 //                       writes), with a barrier between sweeps; rows are at dword row * 66 + 1 + lane: 64 consecutive dwords per
@@ -29,16 +27,17 @@
 //   reach_finish_kernel "none" becomes -1, a cell without its bit -2.
 // The host launches rounds until the counter of changed tiles stands still, reading 32 bytes per round: the call blocks.  No
 // cooperative launch, no workgroup waits on another, every device loop ends by its own data, and the rounds are capped.
-// Resource report (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): reach_relax_kernel 58 VGPRs, 90 SGPRs, 27176 bytes of
-// static LDS (6 workgroups per CU of 160 KB), occupancy 6 by registers; reach_pack_kernel and reach_finish_kernel 14 VGPRs,
+// Resource report (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): reach_relax_kernel 58 VGPRs, 88 SGPRs, 27176 bytes of
+// static LDS (6 workgroups per CU of 160 KB), occupancy 6 by registers; reach_finish_kernel 14 VGPRs,
 // reach_seed_kernel 12, no LDS, occupancy 8; every kernel 0 bytes of scratch.  No per-lane arrays indexed at run time, no inline
 // assembly.
 #include <limits.h>
 
 #include "map_field.hpp"
 #include "map_reach.hpp"
+#include "map_region.hpp"
+#include "map_sweeps.hpp"
 #include "stage_timing.hpp"
-#include "workspace.hpp"
 
 namespace svoslam {
 
@@ -59,19 +58,6 @@ static_assert(sizeof(ReachControl) <= kControlBytes, "the control record and the
 
 __device__ inline int load_steps(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ inline void store_steps(int32_t *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__global__ __launch_bounds__(256) void reach_pack_kernel(int32_t *__restrict__ steps, int nx, int wpr, long long words,
-                                                         unsigned long long *__restrict__ bits) {
-  const long long word = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);  // one wavefront per row word
-  if (word >= words) return;
-  const int lane = threadIdx.x & 63;
-  const int x = (int)(word % wpr) * 64 + lane;
-  const long long at = (word / wpr) * nx + x;
-  const bool in = x < nx;
-  const unsigned long long row_word = __ballot(in && steps[at] == -1);
-  if (in) steps[at] = kNone;
-  if (lane == 0) bits[word] = row_word;
-}
 
 __global__ __launch_bounds__(256) void reach_seed_kernel(const int32_t *__restrict__ seeds, int n, int ox, int oy, int oz, int nx, int ny,
                                                          int nz, int wpr, int tiles_x, int tiles_y,
@@ -137,73 +123,23 @@ __global__ __launch_bounds__(256) void reach_relax_kernel(int32_t *__restrict__ 
       if (lane == 0) v = min(v, s[at - 1] + 1);
       if (lane == 63) v = min(v, s[at + 1] + 1);
       if (!((tw >> lane) & 1ull)) v = kNone;
-#pragma unroll
-      for (int k = 1; k < 64; k *= 2) {  // from below: cells lane - k .. lane all traversable
-        const int u = __shfl_up(v, k);
-        const unsigned long long run = ((2ull << k) - 1ull) << (lane >= k ? lane - k : 0);
-        if (lane >= k && (tw & run) == run) v = min(v, u + k);
-      }
-#pragma unroll
-      for (int k = 1; k < 64; k *= 2) {  // from above: cells lane .. lane + k
-        const int u = __shfl_down(v, k);
-        const unsigned long long run = ((2ull << k) - 1ull) << lane;
-        if (lane + k < 64 && (tw & run) == run) v = min(v, u + k);
-      }
+      v = sweep_row<1>(v, tw, lane);
       if (v < before) { s[at] = v; changed = 1; }
     }
     __syncthreads();
     // y: a lane per (x, z) column
     for (int z = w; z < kTileZ; z += 4) {
-      const int col = (z + 1) * kRowsY * kRowPitch + 1 + lane;
-      int prev = s[col];
-#pragma unroll
-      for (int y = 0; y < kTileY; y++) {
-        const int at = col + (y + 1) * kRowPitch, v = s[at];
-        if ((row_bits[z * 8 + y] >> lane) & 1ull) {
-          prev = min(v, prev + 1);
-          if (prev < v) { s[at] = prev; changed = 1; }
-        } else {
-          prev = kNone;
-        }
-      }
-      prev = s[col + (kTileY + 1) * kRowPitch];
-#pragma unroll
-      for (int y = kTileY - 1; y >= 0; y--) {
-        const int at = col + (y + 1) * kRowPitch, v = s[at];
-        if ((row_bits[z * 8 + y] >> lane) & 1ull) {
-          prev = min(v, prev + 1);
-          if (prev < v) { s[at] = prev; changed = 1; }
-        } else {
-          prev = kNone;
-        }
-      }
+      int32_t *col = s + (z + 1) * kRowsY * kRowPitch + 1 + lane;  // the halo cell below the column; the one above is 9 rows on
+      changed |= sweep_column<1, kNone, kRowPitch, 1, true>(col + kRowPitch, row_bits + z * 8, lane, col[0]);
+      changed |= sweep_column<1, kNone, kRowPitch, 1, false>(col + kRowPitch, row_bits + z * 8, lane, col[(kTileY + 1) * kRowPitch]);
     }
     __syncthreads();
     // z: a lane per (x, y) column
     for (int y = w; y < kTileY; y += 4) {
-      const int col = (y + 1) * kRowPitch + 1 + lane;
-      int prev = s[col];
-#pragma unroll
-      for (int z = 0; z < kTileZ; z++) {
-        const int at = col + (z + 1) * kRowsY * kRowPitch, v = s[at];
-        if ((row_bits[z * 8 + y] >> lane) & 1ull) {
-          prev = min(v, prev + 1);
-          if (prev < v) { s[at] = prev; changed = 1; }
-        } else {
-          prev = kNone;
-        }
-      }
-      prev = s[col + (kTileZ + 1) * kRowsY * kRowPitch];
-#pragma unroll
-      for (int z = kTileZ - 1; z >= 0; z--) {
-        const int at = col + (z + 1) * kRowsY * kRowPitch, v = s[at];
-        if ((row_bits[z * 8 + y] >> lane) & 1ull) {
-          prev = min(v, prev + 1);
-          if (prev < v) { s[at] = prev; changed = 1; }
-        } else {
-          prev = kNone;
-        }
-      }
+      constexpr int kPlane = kRowsY * kRowPitch;
+      int32_t *col = s + (y + 1) * kRowPitch + 1 + lane;
+      changed |= sweep_column<1, kNone, kPlane, 8, true>(col + kPlane, row_bits + y, lane, col[0]);
+      changed |= sweep_column<1, kNone, kPlane, 8, false>(col + kPlane, row_bits + y, lane, col[(kTileZ + 1) * kPlane]);
     }
     again = __syncthreads_or(changed);  // also the barrier in front of the next pass's x sweep
   } while (again);
@@ -259,46 +195,32 @@ int pool_reach_field(svoslam_workspace *ws, const svoslam_pool *pool, int depth,
                      int32_t r, const int32_t *d_seeds, int32_t n_seeds, int32_t *d_steps, svoslam_reach_stats *stats,
                      hipStream_t stream) {
   if (stats) stats->rounds = stats->tile_runs = stats->seeds_used = 0;
-  if (!ws || !origin || !dims || depth < 1 || depth > SVOSLAM_MAX_DEPTH) return SVOSLAM_ERR_INVALID_ARG;
-  if (r < 0 || r > SVOSLAM_MAX_RADIUS_CELLS || n_seeds < 0 || (n_seeds > 0 && !d_seeds)) return SVOSLAM_ERR_INVALID_ARG;
-  bool nothing = false;
-  for (int a = 0; a < 3; a++) {
-    if (dims[a] < 0 || origin[a] < 0 || (long long)origin[a] + dims[a] > (1ll << depth)) return SVOSLAM_ERR_INVALID_ARG;
-    nothing = nothing || dims[a] == 0;
-  }
-  if (nothing) return SVOSLAM_OK;
-  const long long nx = dims[0], ny = dims[1], nz = dims[2];
-  const long long wpr = (nx + 63) / 64, words = wpr * ny * nz;  // <= the field's own row words: within its limits
+  if (!ws || r < 0 || r > SVOSLAM_MAX_RADIUS_CELLS || n_seeds < 0 || (n_seeds > 0 && !d_seeds)) return SVOSLAM_ERR_INVALID_ARG;
+  RegionPlan own;  // the region itself: its row words are <= the field's own, within its limits
+  SVO_TRY(plan_region(depth, origin, dims, 0, &own));
+  if (own.nothing) return SVOSLAM_OK;
+  const long long nx = own.nx, ny = own.ny, nz = own.nz, wpr = own.wpr, words = own.words;
   const long long tiles_x = wpr, tiles_y = (ny + kTileY - 1) / kTileY, tiles_z = (nz + kTileZ - 1) / kTileZ;
   const long long tiles = tiles_x * tiles_y * tiles_z;
-  // a launch takes at most 2^32 - 1 work-items: decided here, before anything is allocated or written (the products cannot
-  // overflow: every side is <= 2^16)
-  if ((long long)dims[0] * dims[1] * dims[2] <= INT_MAX && tiles * 256 > 0xFFFFFFFFll) {
+  // a launch takes at most 2^32 - 1 work-items: decided here, before anything is allocated or written
+  if (own.n_out <= INT_MAX && tiles * 256 > 0xFFFFFFFFll) {
     set_last_error_text("svoslam_pool_reach_field: %lld x %lld x %lld cells are %lld tiles, more than one launch takes (2^24 - 1)", nx,
                         ny, nz, tiles);
     return SVOSLAM_ERR_POOL_LIMIT;
   }
   // the traversable set, as the field's -1, in d_steps: the rest of the argument checks, the field's limits (decided before
   // anything is allocated), the drain of pending fusions and the field's own slots are pool_distance_field's
-  svoslam::DeviceBuffer *slots[5] = {&ws->field_bits, &ws->field_a, &ws->field_b, &ws->reach_bits, &ws->reach_flags};
-  size_t had[5];
-  for (int k = 0; k < 5; k++) had[k] = slots[k]->bytes;
+  SlotRollback grown(ws, &ws->reach_bits, &ws->reach_flags);
   AdoptedBracket bracket(stream);
   SVO_TRY(pool_distance_field(ws, pool, depth, origin, dims, r, d_steps, nullptr, stream, &bracket.token));
   int rc = ws->reach_bits.reserve((size_t)words * 8);
   if (rc == SVOSLAM_OK) rc = ws->reach_flags.reserve(kControlBytes + (size_t)tiles * 8);
-  if (rc != SVOSLAM_OK) {  // the slots this call grew do not stay behind; the field's launches have finished before theirs go
-    (void)hipStreamSynchronize(stream);
-    for (int k = 0; k < 5; k++)
-      if (slots[k]->bytes != had[k]) slots[k]->release();
-    return rc;
-  }
+  if (rc != SVOSLAM_OK) return grown.undo(rc, stream);
   unsigned long long *bits = ws->reach_bits.as<unsigned long long>();
   ReachControl *ctl = ws->reach_flags.as<ReachControl>();
   int *flags = reinterpret_cast<int *>(ws->reach_flags.as<char>() + kControlBytes);
   SVO_HIP(hipMemsetAsync(ctl, 0, kControlBytes + (size_t)tiles * 8, stream));
-  reach_pack_kernel<<<cdiv(words, 4), 256, 0, stream>>>(d_steps, (int)nx, (int)wpr, words, bits);
-  SVO_LAUNCH_CHECK();
+  SVO_TRY(region_pack(own, d_steps, false, &kNone, bits, stream));  // d_steps becomes the working array in place
   if (n_seeds > 0) {
     reach_seed_kernel<<<cdiv(n_seeds, 256), 256, 0, stream>>>(d_seeds, n_seeds, origin[0], origin[1], origin[2], (int)nx, (int)ny, (int)nz,
                                                               (int)wpr, (int)tiles_x, (int)tiles_y, bits, d_steps, flags, ctl);

@@ -5,9 +5,7 @@
 //
 // With the region inflated by R and clipped to the root (every cell between a counting viewpoint within range and its target lies
 // in it, because it lies in their bounding box):
-//   vis_raster_kernel   field_raster_kernel a third time: one wavefront per 64-bit row word, one descent per cell, a ballot.  An
-//                       instantiation of this file's own, so that map_field.hip's and map_nearest.hip's generated code stay as they
-//                       are; folding the three copies into one is a refactor of its own.
+//   the raster          map_region.hip's region_raster_kernel, as the distance field runs it: the occupied cells as 64-bit row words.
 //   sight_kernel        one lane per output cell, x fastest.  The loop over the viewpoints is uniform across the wavefront and the
 //                       viewpoint is read through a uniform index.  Per viewpoint the range test, then the walk from v towards q.
 //                       With D = q - v the segment crosses axis a's i-th face at (2 i - 1) / (2 |D_a|); the kernel keeps per axis
@@ -19,37 +17,17 @@
 //                       walk stops on entering q without testing it, after the side cells of a tie that ends there; it leaves at
 //                       the first set bit.  Neighbouring lanes share v and end next to each other, so their first steps read the
 //                       same row words.  The three keys, their increments and the current cell are named scalars.
-// Resource report (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): vis_raster_kernel 18 VGPRs / 31 SGPRs, sight_kernel 42 VGPRs / 62 SGPRs;
-// both 0 bytes of scratch, no LDS.  No per-lane arrays; every store is a vector store from plain C++.
-#include <limits.h>
-
-#include "map_descend.hpp"
+// Resource report (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): sight_kernel 42 VGPRs / 62 SGPRs, 0 bytes of scratch, no
+// LDS.  No per-lane arrays; every store is a vector store from plain C++.
+#include "map_region.hpp"
 #include "map_visibility.hpp"
 #include "stage_timing.hpp"
-#include "workspace.hpp"
 
 namespace svoslam {
 
 namespace {
 
 constexpr long long kNever = 1ll << 62;  // the key of an axis along which the segment does not move
-
-__global__ __launch_bounds__(256) void vis_raster_kernel(const uint32_t *__restrict__ pool, int d, int x0, int y0, int z0, int x1,
-                                                         int wpr, int iny, long long words, unsigned long long *__restrict__ bits) {
-  const long long word = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);  // one wavefront per row word
-  if (word >= words) return;
-  const int lane = threadIdx.x & 63;
-  const long long row = word / wpr;
-  const int x = x0 + (int)(word % wpr) * 64 + lane, y = y0 + (int)(row % iny), z = z0 + (int)(row / iny);
-  bool hit = false;
-  if (x < x1) {
-    uint32_t nd = 0u;
-    uint2 w = make_uint2(0u, 0u);
-    descend<false>(pool, morton3(x, y, z), d, x, y, z, 0, 0, 0, 0, nd, w, hit);
-  }
-  const unsigned long long row_word = __ballot(hit);
-  if (lane == 0) bits[word] = row_word;
-}
 
 // the bit of cell (x, y, z) of the inflated region (coordinates relative to its first cell)
 __device__ __forceinline__ bool occupied(const unsigned long long *__restrict__ bits, int wpr, int leny, int x, int y, int z) {
@@ -118,48 +96,24 @@ __global__ __launch_bounds__(256) void sight_kernel(const unsigned long long *__
 
 int pool_visibility_field(svoslam_workspace *ws, const svoslam_pool *pool, int depth, const int32_t origin[3], const int32_t dims[3],
                           int32_t R, const int32_t *d_views, int32_t n_views, uint32_t *d_mask, int32_t *d_count, hipStream_t stream) {
-  if (!ws || !origin || !dims || depth < 1 || depth > SVOSLAM_MAX_DEPTH) return SVOSLAM_ERR_INVALID_ARG;
-  if (R < 0 || R > SVOSLAM_MAX_RADIUS_CELLS) return SVOSLAM_ERR_INVALID_ARG;  // 3 R^2 fits an int32, a key fits an int64
-  if (n_views < 0 || (n_views > 0 && !d_views)) return SVOSLAM_ERR_INVALID_ARG;
+  if (!ws || n_views < 0 || (n_views > 0 && !d_views)) return SVOSLAM_ERR_INVALID_ARG;
   if (d_mask && n_views > SVOSLAM_MAX_VIEWS_MASK) return SVOSLAM_ERR_INVALID_ARG;  // a bit per viewpoint
-  const long long N = 1ll << depth;
-  long long lo[3], len[3];  // the inflated region: first cell and cells per axis
-  bool nothing = false;
-  for (int a = 0; a < 3; a++) {
-    if (dims[a] < 0 || origin[a] < 0 || (long long)origin[a] + dims[a] > N) return SVOSLAM_ERR_INVALID_ARG;
-    nothing = nothing || dims[a] == 0;
-    lo[a] = origin[a] - R > 0 ? origin[a] - R : 0;
-    const long long end = (long long)origin[a] + dims[a] + R < N ? (long long)origin[a] + dims[a] + R : N;
-    len[a] = end - lo[a];
-  }
-  if (nothing) return SVOSLAM_OK;
-  if (!pool || !pool->d_data || (!d_mask && !d_count)) return SVOSLAM_ERR_INVALID_ARG;
-  const long long nx = dims[0], ny = dims[1], nz = dims[2];
-  const long long wpr = (len[0] + 63) / 64, words = wpr * len[1] * len[2], n_out = nx * ny * nz;
-  const long long limit = INT_MAX;  // every side is <= 2^16, so neither product overflows an int64
-  if (n_out > limit) {
-    set_last_error_text("svoslam_pool_visibility_field: %lld x %lld x %lld cells are more than 2^31 - 1", nx, ny, nz);
-    return SVOSLAM_ERR_POOL_LIMIT;
-  }
-  if (words > limit) {
-    set_last_error_text("svoslam_pool_visibility_field: the region inflated by %d cells (%lld x %lld x %lld) needs more than 2^31 - 1 "
-                        "row words", R, len[0], len[1], len[2]);
-    return SVOSLAM_ERR_POOL_LIMIT;
-  }
-  if (pool->pending > 0) SVO_HIP(hipStreamSynchronize(stream));  // as pool_distance_field drains pending asynchronous fusions
-  const int rc = ws->vis_bits.reserve((size_t)words * 8);
+  RegionPlan p;  // R <= SVOSLAM_MAX_RADIUS_CELLS: 3 R^2 fits an int32, a key fits an int64
+  SVO_TRY(plan_region(depth, origin, dims, R, &p));
+  if (p.nothing) return SVOSLAM_OK;
+  if (!d_mask && !d_count) return SVOSLAM_ERR_INVALID_ARG;
+  SVO_TRY(admit_region("svoslam_pool_visibility_field", pool, p, R, false, stream));
+  const int rc = ws->vis_bits.reserve((size_t)p.words * 8);
   if (rc != SVOSLAM_OK) {  // nothing the call allocated stays behind
     ws->vis_bits.release();
     return rc;
   }
   unsigned long long *bits = ws->vis_bits.as<unsigned long long>();
   StageScope query(kStageQuery, stream);
-  vis_raster_kernel<<<cdiv(words, 4), 256, 0, stream>>>(pool->d_data, depth, (int)lo[0], (int)lo[1], (int)lo[2], (int)(lo[0] + len[0]),
-                                                        (int)wpr, (int)len[1], words, bits);
-  SVO_LAUNCH_CHECK();
-  sight_kernel<<<cdiv(n_out, 256), 256, 0, stream>>>(bits, (int)wpr, (int)len[1], (int)lo[0], (int)lo[1], (int)lo[2], origin[0],
-                                                     origin[1], origin[2], (int)nx, (int)ny, (int)N, R, d_views, n_views, (int)n_out,
-                                                     d_mask, d_count);
+  SVO_TRY(region_raster(pool, depth, p, false, bits, stream));
+  sight_kernel<<<cdiv(p.n_out, 256), 256, 0, stream>>>(bits, (int)p.wpr, (int)p.len[1], (int)p.lo[0], (int)p.lo[1], (int)p.lo[2],
+                                                       origin[0], origin[1], origin[2], (int)p.nx, (int)p.ny, 1 << depth, R, d_views,
+                                                       n_views, (int)p.n_out, d_mask, d_count);
   SVO_LAUNCH_CHECK();
   return SVOSLAM_OK;
 }

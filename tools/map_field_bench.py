@@ -93,7 +93,7 @@ def main():
             args.frames, args.runs, pkg.device_arch(), datetime.date.today().isoformat(), args.runs),
         "map: %d frames of the synthetic stream, %dx%d, depth %d, corrected tracker: %d nodes; regions about cell %s, the median of the last frame's fused points" % (
             args.frames, w, h, depth, nodes, about.tolist()),
-        "field_raster_kernel 18 VGPRs, field_x_kernel 16, field_pass_kernel 13 (LDS) / 10 (global), 0 bytes of scratch; LDS (64 + 2 R) * 256 bytes per one-wavefront workgroup (compiler's resource report)",
+        "region_raster_kernel 18 VGPRs, edt_x_kernel<false> 16, edt_pass_kernel<kLds, false> 13 (LDS) / 10 (global), 0 bytes of scratch; LDS (64 + 2 R) * 256 bytes per one-wavefront workgroup (compiler's resource report)",
     ]
     for title, dims in (("block", (256, 256, 64)), ("mid-plane", (512, 1, 512))):
         origin = [int(np.clip(about[a] - dims[a] // 2, 0, n_side - dims[a])) for a in range(3)]

@@ -93,7 +93,7 @@ def main():
             args.frames, args.runs, pkg.device_arch(), datetime.date.today().isoformat(), args.runs),
         "map: %d frames of the synthetic stream, %dx%d, depth %d, corrected tracker: %d nodes; regions about cell %s, the median of the last frame's fused points" % (
             args.frames, w, h, depth, nodes, about.tolist()),
-        "nearest_raster_kernel 18 VGPRs, nearest_x_kernel 17, nearest_pass_kernel 18 (LDS) / 14 (global), nearest_resolve_kernel 15 (node / colour) / 11, 0 bytes of scratch; LDS (64 + 2 R) * 256 bytes per one-wavefront workgroup (compiler's resource report)",
+        "region_raster_kernel 18 VGPRs, edt_x_kernel<true> 17, edt_pass_kernel<kLds, true> 18 (LDS) / 14 (global), nearest_resolve_kernel 15 (node / colour) / 11, 0 bytes of scratch; LDS (64 + 2 R) * 256 bytes per one-wavefront workgroup (compiler's resource report)",
         "kernels: HIP events around the call's one bracket; call: wall clock of the Python call + a device synchronisation, which for nearest_field includes the binding's unpacking of cell into cell_xyz (torch kernels outside the bracket)",
     ]
     for title, dims in (("block", (256, 256, 64)), ("mid-plane", (512, 1, 512))):
