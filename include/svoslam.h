@@ -738,6 +738,72 @@ int svoslam_score_poses(svoslam_workspace *ws, const int32_t *d_dist2, int32_t m
 /* diagnostics: the device pointer and size in bytes of the workspace's scoring slot (the per-pose records; NULL / 0 before the
  * first call that needs them), as svoslam_workspace_field_buffers shows the distance field's.  Host only. */
 int svoslam_workspace_score_buffers(const svoslam_workspace *ws, void *d_ptrs[1], uint64_t bytes[1]);
+/* Path planning in a map region (no reference counterpart; specification here and in DESIGN.md section 21): the reach field with a
+ * weight per cell -- a cost-to-go field whose cheapest paths keep away from obstacles where they can, as the inflation layer in
+ * front of every navigation stack's planner makes them -- and the paths themselves, traced down any such field for many starts at
+ * once.  Exact, in integers.
+ *
+ * svoslam_pool_cost_field
+ *   d, N, the occupied set, the region and the output order are exactly those of svoslam_pool_distance_field.
+ *   Traversable set T and seeds: with r = clearance_cells (0..SVOSLAM_MAX_RADIUS_CELLS), T and the rule for which seeds count are
+ *     exactly svoslam_pool_reach_field's: a region cell is in T iff no occupied cell of the WHOLE root lies within squared distance
+ *     r^2 of it; a seed (d_seeds, n_seeds triples of int32 absolute cells, device memory) counts if it lies in the region and in T.
+ *   Weight: R = comfort_cells, r <= R <= SVOSLAM_MAX_RADIUS_CELLS.  For q in T let D be the squared distance in cells to the nearest
+ *     occupied cell of the whole root -- what svoslam_pool_distance_field with radius R writes, -1 meaning D > R^2.  If D > R^2,
+ *     w(q) = 1.  Otherwise let j be the integer with (j - 1)^2 < D <= j^2, so r + 1 <= j <= R: w(q) = 1 + h_ring_cost[j - r - 1].
+ *     h_ring_cost is HOST memory, R - r entries, each in 0..SVOSLAM_MAX_RING_COST; it may be NULL when R == r.  The profile need not
+ *     be monotone.
+ *   Output: d_cost, dims[0] * dims[1] * dims[2] values of type int32 in device memory, x fastest, indexed as d_dist2 is.  The value
+ *     at q is -2 if q is not in T; otherwise the minimum of the sum of w(p) over a path's cells EXCEPT ITS SEED, over the paths of
+ *     face-neighbour moves from a counted seed to q whose every cell is in T and IN THE REGION: 0 at a counted seed, -1 if there is
+ *     no such path.  Only these values are specified, not how they are computed; the result does not depend on scheduling.  With
+ *     every ring cost 0, or with R == r, the field equals svoslam_pool_reach_field's d_steps value for value.  stats (may be NULL):
+ *     seeds_used as in the reach field; max_weight = 1 + the largest ring cost (1 without rings); rounds and tile_runs are
+ *     diagnostics with no specified value.
+ *   Conventions: the reach field's -- any pool; pending asynchronous fusions are drained first; a deferred commit's pool is read in
+ *     its old state; THE CALL BLOCKS, the host reads one small convergence record (32 bytes) per round; the intermediates (the
+ *     distance field's, and three of its own: the bit rows of T, a 16-bit weight per cell, and the control record with the tile
+ *     flags and the ring costs) live in grow-only slots of the workspace, so a second call of the same size allocates nothing.
+ *   Errors: a zero entry of dims is SVOSLAM_OK and launches nothing, if the other arguments are valid.  SVOSLAM_ERR_INVALID_ARG:
+ *     those of svoslam_pool_reach_field (d_cost for d_steps), comfort_cells < clearance_cells or > SVOSLAM_MAX_RADIUS_CELLS, NULL
+ *     h_ring_cost with R > r, an entry of it outside 0..SVOSLAM_MAX_RING_COST.  SVOSLAM_ERR_POOL_LIMIT, decided before anything is
+ *     allocated or written: the limits of svoslam_pool_distance_field with radius_cells = R; more than 2^24 - 1 tiles of 64 x 8 x 8
+ *     cells; n_out * max_weight >= 2^30 (the value of "not reached": a path has fewer cells than the region, so below this limit no
+ *     finite cost can collide with it).  SVOSLAM_ERR_OOM: an allocation failed; the slots the call grew are released, after the
+ *     stream has drained.  SVOSLAM_ERR_HIP with a text in svoslam_last_error: the round cap (tiles * cells per tile + 1) was
+ *     reached, which the argument of section 21 rules out.
+ *
+ * svoslam_field_trace_paths (no pool, no workspace)
+ *   d_field: any int32 array in device memory laid out as d_cost / d_steps over the region origin_cell .. origin_cell + dims.  A
+ *     value >= 0 is a cost-to-go, a negative value means the cell cannot be entered.  d_starts: n_starts triples (x, y, z) of int32
+ *     absolute cells, in device memory.
+ *   The path of a start: if the start lies outside the region or its value is negative, the length is 0 and nothing is stored.
+ *     Otherwise the path begins at the start; from a cell of value v > 0 it moves to a face neighbour INSIDE THE REGION whose value
+ *     v' satisfies 0 <= v' < v, among those to the one with the smallest v', on a tie to the first in the order -x, +x, -y, +y, -z,
+ *     +z; it ends at a cell of value 0.  On a field of svoslam_pool_cost_field or svoslam_pool_reach_field this is a cheapest /
+ *     shortest path, and its cost summed by the field's own weights equals the value at the start.  The values fall strictly, so
+ *     the walk is bounded by its data.
+ *   Outputs: d_lengths[i] = the number of cells of the whole path, start and final cell included, EVEN WHEN IT EXCEEDS max_cells;
+ *     d_paths [n_starts][max_cells][3] int32 receives the first min(length, max_cells) cells as absolute (x, y, z), the entries
+ *     behind them are not written (d_paths may be NULL if max_cells == 0).  On an array that is not such a field the walk may reach
+ *     a cell of value > 0 without a lower enterable neighbour: it stops there, and the length is MINUS the number of cells walked.
+ *   Asynchronous on `stream`, nothing is read back.  All region arithmetic is in 64 bits.
+ *   Errors: SVOSLAM_ERR_INVALID_ARG: NULL origin_cell or dims; a negative entry of dims, n_starts or max_cells; with n_starts > 0 a
+ *     NULL d_starts or d_lengths, a NULL d_field with a non-empty region, a NULL d_paths with max_cells > 0.
+ *     SVOSLAM_ERR_POOL_LIMIT: more than 2^31 - 1 cells, or n_starts * max_cells * 3 > 2^31 - 1.  A zero entry of dims gives lengths 0. */
+#define SVOSLAM_MAX_RING_COST 65534
+typedef struct { int32_t rounds, tile_runs, seeds_used, max_weight; } svoslam_plan_stats;
+int svoslam_pool_cost_field(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                            const int32_t dims[3], int32_t clearance_cells, int32_t comfort_cells,
+                            const int32_t *h_ring_cost /* HOST, comfort_cells - clearance_cells entries */, const int32_t *d_seeds,
+                            int32_t n_seeds, int32_t *d_cost, svoslam_plan_stats *stats /* may be NULL */, void *stream);
+int svoslam_field_trace_paths(const int32_t *d_field, const int32_t origin_cell[3], const int32_t dims[3], const int32_t *d_starts,
+                              int32_t n_starts, int32_t max_cells, int32_t *d_paths /* [n_starts][max_cells][3], may be NULL if max_cells == 0 */,
+                              int32_t *d_lengths /* [n_starts] */, void *stream);
+/* diagnostics: the device pointers and sizes in bytes of the workspace's three cost-field slots (the bit rows of T; the weights;
+ * the control record with the tile flags and the ring costs; NULL / 0 before the first call), as svoslam_workspace_reach_buffers
+ * shows the reach field's.  Host only. */
+int svoslam_workspace_plan_buffers(const svoslam_workspace *ws, void *d_ptrs[3], uint64_t bytes[3]);
 /* The library's own sort and scan, exposed for tests and tools (no reference counterpart).  Every map operation sorts Morton keys
  * with the stable LSD radix sort of csrc/radix_sort.hip and compacts with its exclusive scan; these two calls reach them with
  * arguments of the caller's choosing, where the map's calls choose the form and the digit width from n.  All arrays are in device
@@ -922,7 +988,7 @@ int svoslam_cone_trace_timing_read(float *h_ms_sum, int32_t *h_launches);
 #define SVOSLAM_STAGE_SURFACE_BFS 9    /* extract_surface_mesh: the occupied cells (incl. one readback per level) */
 #define SVOSLAM_STAGE_SURFACE_FACES 10 /* extract_surface_mesh: face masks + scan (incl. the count readback) | emission: two brackets per call, the host's allocations between them are outside */
 #define SVOSLAM_STAGE_SURFACE_WELD 11  /* extract_surface_mesh: corner sort + run heads + scan (incl. the count readback) | scatter: two brackets per call likewise */
-#define SVOSLAM_STAGE_QUERY 12         /* svoslam_pool_cast_rays / _query_points / _count_boxes / _nearest_occupied: the kernel, one bracket per call; svoslam_pool_distance_field: its four launches, one bracket per call; svoslam_pool_reach_field: the field's launches and every launch and readback of the relaxation, one bracket per call; svoslam_pool_label_components: the field's launches and its own, one bracket per call; svoslam_pool_nearest_field: its five launches, one bracket per call; svoslam_pool_visibility_field: its two launches, one bracket per call; svoslam_score_poses: its one to three launches, one bracket per call */
+#define SVOSLAM_STAGE_QUERY 12         /* svoslam_pool_cast_rays / _query_points / _count_boxes / _nearest_occupied: the kernel, one bracket per call; svoslam_pool_distance_field: its four launches, one bracket per call; svoslam_pool_reach_field: the field's launches and every launch and readback of the relaxation, one bracket per call; svoslam_pool_label_components: the field's launches and its own, one bracket per call; svoslam_pool_nearest_field: its five launches, one bracket per call; svoslam_pool_visibility_field: its two launches, one bracket per call; svoslam_score_poses: its one to three launches, one bracket per call; svoslam_pool_cost_field: the field's launches and every launch and readback of the relaxation, one bracket per call; svoslam_field_trace_paths: its launch, one bracket per call */
 #define SVOSLAM_STAGE_COUNT 13
 int svoslam_stage_timing(uint32_t mask);
 int svoslam_stage_timing_read(int32_t stage, float *h_ms_sum, int32_t *h_pairs);

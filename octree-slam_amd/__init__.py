@@ -50,6 +50,10 @@ class _ReachStats(C.Structure):
     _fields_ = [("rounds", C.c_int32), ("tile_runs", C.c_int32), ("seeds_used", C.c_int32)]
 
 
+class _PlanStats(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("tile_runs", C.c_int32), ("seeds_used", C.c_int32), ("max_weight", C.c_int32)]
+
+
 class _ComponentStats(C.Structure):
     _fields_ = [("components", C.c_int32), ("largest", C.c_int32), ("tile_passes", C.c_int32), ("unions", C.c_int32)]
 
@@ -223,6 +227,10 @@ SIGNATURES = {
     "svoslam_score_poses": (C.c_int, [_vp, _vp, _i32, _fp, _f32, C.POINTER(_i32), C.POINTER(_i32), _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp,
                                       _vp, _vp, _vp, _vp]),
     "svoslam_workspace_score_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "svoslam_pool_cost_field": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, C.POINTER(_i32), _vp,
+                                          _i32, _vp, C.POINTER(_PlanStats), _vp]),
+    "svoslam_field_trace_paths": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), _vp, _i32, _i32, _vp, _vp, _vp]),
+    "svoslam_workspace_plan_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
     "svoslam_sort_words": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "svoslam_exclusive_scan_u32": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp]),
     "svoslam_malloc": (C.c_int, [C.POINTER(_vp), C.c_size_t]),
@@ -400,6 +408,12 @@ class Workspace:
         ptrs, sizes = (_vp * 2)(), (C.c_uint64 * 2)()
         check(lib().svoslam_workspace_reach_buffers(self._h, ptrs, sizes))
         return [(int(ptrs[k] or 0), int(sizes[k])) for k in range(2)]
+
+    def plan_buffers(self):
+        """svoslam_workspace_plan_buffers: [(device pointer, bytes)] of the three cost-field slots (diagnostics)"""
+        ptrs, sizes = (_vp * 3)(), (C.c_uint64 * 3)()
+        check(lib().svoslam_workspace_plan_buffers(self._h, ptrs, sizes))
+        return [(int(ptrs[k] or 0), int(sizes[k])) for k in range(3)]
 
     def component_buffers(self):
         """svoslam_workspace_component_buffers: [(device pointer, bytes)] of the two component slots (diagnostics)"""
@@ -937,6 +951,123 @@ def reach_field(ws, pool, max_depth, origin, dims, clearance_cells, seeds, as_te
     if stats is not None:
         stats.update(rounds=int(st.rounds), tile_runs=int(st.tile_runs), seeds_used=int(st.seeds_used))
     return out if as_tensor else out.cpu().numpy()
+
+
+MAX_RING_COST = 65534                                                   # include/svoslam.h SVOSLAM_MAX_RING_COST
+
+
+def _cells_tensor(cells, what):
+    """[n, 3] absolute cells, an array or an int32 cuda tensor -> a contiguous int32 cuda tensor"""
+    import torch
+    if isinstance(cells, torch.Tensor):
+        if not cells.is_cuda or cells.dtype != torch.int32:
+            raise ValueError("a %s tensor is int32 on the device" % what)
+        return cells.reshape(-1, 3).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(cells, np.int32).reshape(-1, 3))).cuda()
+
+
+def cost_field(ws, pool, max_depth, origin, dims, clearance_cells, comfort_cells, ring_cost, seeds, as_tensor=False, stats=None):
+    """svoslam_pool_cost_field: reach_field with a weight per cell.  Entering a traversable cell costs 1 + ring_cost[j - clearance_cells
+    - 1] when its nearest occupied cell is in ring j ((j - 1)^2 < dist2 <= j^2, clearance_cells < j <= comfort_cells), and 1 beyond
+    comfort_cells; `ring_cost` holds comfort_cells - clearance_cells integers in 0 .. MAX_RING_COST.  The value of a cell is the
+    cheapest sum over a path from any of `seeds` ([n, 3] absolute cells: an array, or an int32 cuda tensor), the seed's own weight
+    left out: 0 at a seed that counts, -1 where no path leads, -2 where the cell is blocked.  With all ring costs 0 it is
+    reach_field.  -> int32 [nz, ny, nx], a numpy array, or with as_tensor a cuda tensor.  The call blocks either way.  `stats`: a
+    dict that receives rounds, tile_runs, seeds_used and max_weight."""
+    import torch
+    o, n = [int(v) for v in origin], [int(v) for v in dims]
+    if len(o) != 3 or len(n) != 3:
+        raise ValueError("origin and dims are three cells each (x, y, z)")
+    ring = [int(v) for v in np.asarray(ring_cost if ring_cost is not None else [], np.int64).reshape(-1)]
+    if len(ring) != max(int(comfort_cells) - int(clearance_cells), 0):
+        raise ValueError("ring_cost holds comfort_cells - clearance_cells entries")
+    if any(v < 0 or v > MAX_RING_COST for v in ring):
+        raise ValueError("a ring cost lies in 0 .. %d" % MAX_RING_COST)
+    t_seeds = _cells_tensor(seeds, "seeds")
+    count = int(t_seeds.shape[0])
+    out = torch.empty([max(v, 0) for v in reversed(n)], dtype=torch.int32, device="cuda")
+    st = _PlanStats()
+    check(lib().svoslam_pool_cost_field(ws._h, C.byref(pool._p), int(max_depth), (_i32 * 3)(*o), (_i32 * 3)(*n), int(clearance_cells),
+                                        int(comfort_cells), (_i32 * len(ring))(*ring) if ring else None, _ptr(t_seeds) if count else None,
+                                        count, _ptr(out), C.byref(st), _stream()))
+    if stats is not None:
+        stats.update(rounds=int(st.rounds), tile_runs=int(st.tile_runs), seeds_used=int(st.seeds_used), max_weight=int(st.max_weight))
+    return out if as_tensor else out.cpu().numpy()
+
+
+def trace_paths(field, origin, dims, starts, max_cells, as_tensor=False):
+    """svoslam_field_trace_paths: from every start ([n, 3] absolute cells: an array, or an int32 cuda tensor) down `field` (int32 [nz,
+    ny, nx] over origin[3] .. origin + dims[3], as cost_field and reach_field return it: an array or a cuda tensor), always to the
+    face neighbour in the region with the smallest value below the cell's own, the first of -x +x -y +y -z +z on a tie, until a cell
+    of value 0.  -> (paths int32 [n, max_cells, 3], lengths int32 [n]): lengths[i] counts the cells of the whole path, start and
+    final cell included, even beyond max_cells; only the first min(length, max_cells) rows of paths[i] are written, the rest are
+    -1 here.  Length 0: the start is outside the region or on a negative value; a negative length: the array is not a cost-to-go
+    field, the walk stopped after that many cells.  numpy arrays, or with as_tensor cuda tensors and nothing is synchronised."""
+    import torch
+    o, n = [int(v) for v in origin], [int(v) for v in dims]
+    if len(o) != 3 or len(n) != 3:
+        raise ValueError("origin and dims are three cells each (x, y, z)")
+    if isinstance(field, torch.Tensor):
+        if not field.is_cuda or field.dtype != torch.int32:
+            raise ValueError("a field tensor is int32 on the device")
+        t_field = field.contiguous()
+    else:
+        t_field = torch.from_numpy(np.ascontiguousarray(np.asarray(field, np.int32))).cuda()
+    if t_field.numel() != max(n[0], 0) * max(n[1], 0) * max(n[2], 0):
+        raise ValueError("the field holds dims[0] * dims[1] * dims[2] values")
+    t_starts = _cells_tensor(starts, "starts")
+    count, cap = int(t_starts.shape[0]), int(max_cells)
+    paths = torch.full((count, max(cap, 0), 3), -1, dtype=torch.int32, device="cuda")
+    lengths = torch.zeros(count, dtype=torch.int32, device="cuda")
+    check(lib().svoslam_field_trace_paths(_ptr(t_field) if t_field.numel() else None, (_i32 * 3)(*o), (_i32 * 3)(*n),
+                                          _ptr(t_starts) if count else None, count, cap, _ptr(paths) if paths.numel() else None,
+                                          _ptr(lengths) if count else None, _stream()))
+    if as_tensor:
+        return paths, lengths
+    return paths.cpu().numpy(), lengths.cpu().numpy()
+
+
+def plan_paths(ws, pool, max_depth, center, edge_length, box, goal, starts, clearance_cells, comfort_cells, ring_cost, max_cells=None):
+    """From every start to the goal (metres) through the box (metres: min xyz, max xyz) of the map, keeping clearance_cells from
+    every occupied cell and paying ring_cost nearer than comfort_cells (cost_field).  The cells of the box are box_to_cells', the
+    goal and the starts the cells that hold them by the same rule; the cost field is seeded at the goal's cell, computed once, and
+    every start is traced down it (trace_paths).  -> None for an empty box, else a dict: cost (the field), origin, dims, cell_size,
+    goal_cell (None outside the root cube), and paths, one dict per start: cell (None outside the root cube), cost and length (None
+    without a path: the start or the goal is outside the box or blocked, or no path joins them), cells int32 [length, 3] from the
+    start to the goal and polyline float64 [length, 3], their centres in metres (both None without a path).  max_cells: at most
+    that many cells of each path are kept (length still counts them all); default: every path whole."""
+    cells = box_to_cells(max_depth, center, edge_length, box)
+    if cells is None:
+        return None
+    lo, hi = cells
+    dims = hi - lo + 1
+
+    def cell_of(point):
+        at = box_to_cells(max_depth, center, edge_length, [float(v) for v in point] * 2)
+        return None if at is None else at[0]
+    goal_cell = cell_of(goal)
+    start_cells = [cell_of(s) for s in np.asarray(starts, np.float64).reshape(-1, 3)]
+    outside = lo - 1                                                    # a cell that is not in the region, for points outside the root
+    cost = cost_field(ws, pool, max_depth, lo, dims, clearance_cells, comfort_cells, ring_cost,
+                      [goal_cell if goal_cell is not None else outside], as_tensor=True)
+    stand_ins = [c if c is not None else outside for c in start_cells]
+    _, lengths = trace_paths(cost, lo, dims, stand_ins, 0)              # the lengths alone: the room the longest path needs
+    room = int(lengths.max()) if len(stand_ins) else 0
+    paths, lengths = trace_paths(cost, lo, dims, stand_ins, room if max_cells is None else min(room, int(max_cells)))
+    cell_size = 2.0 * float(edge_length) / (1 << int(max_depth))
+    corner = np.asarray(center, np.float64) - float(edge_length)
+    cost = cost.cpu().numpy()
+    out = []
+    for k, c in enumerate(start_cells):
+        n = int(lengths[k])
+        if n <= 0:
+            out.append(dict(cell=c, cost=None, length=None, cells=None, polyline=None))
+            continue
+        kept = paths[k, :min(n, paths.shape[1])].copy()
+        rel = c - lo
+        out.append(dict(cell=c, cost=int(cost[rel[2], rel[1], rel[0]]), length=n, cells=kept,
+                        polyline=corner + (kept.astype(np.float64) + 0.5) * cell_size))
+    return dict(cost=cost, origin=lo, dims=dims, cell_size=cell_size, goal_cell=goal_cell, paths=out)
 
 
 COMPONENTS_FREE, COMPONENTS_SOLID = 0, 1                                # include/svoslam.h SVOSLAM_COMPONENTS_*

@@ -11,6 +11,7 @@
 #include "map_components.hpp"
 #include "map_field.hpp"
 #include "map_nearest.hpp"
+#include "map_plan.hpp"
 #include "map_query.hpp"
 #include "map_reach.hpp"
 #include "map_score.hpp"
@@ -489,6 +490,27 @@ int svoslam_workspace_score_buffers(const svoslam_workspace *ws, void *d_ptrs[1]
   if (!ws || !d_ptrs || !bytes) return SVOSLAM_ERR_INVALID_ARG;
   d_ptrs[0] = ws->score_rec.ptr;
   bytes[0] = ws->score_rec.bytes;
+  return SVOSLAM_OK;
+}
+
+int svoslam_pool_cost_field(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                            const int32_t dims[3], int32_t clearance_cells, int32_t comfort_cells, const int32_t *h_ring_cost,
+                            const int32_t *d_seeds, int32_t n_seeds, int32_t *d_cost, svoslam_plan_stats *stats, void *stream) {
+  NEED_DEVICE();
+  return pool_cost_field(ws, pool, max_depth, origin_cell, dims, clearance_cells, comfort_cells, h_ring_cost, d_seeds, n_seeds, d_cost,
+                         stats, S(stream));
+}
+
+int svoslam_field_trace_paths(const int32_t *d_field, const int32_t origin_cell[3], const int32_t dims[3], const int32_t *d_starts,
+                              int32_t n_starts, int32_t max_cells, int32_t *d_paths, int32_t *d_lengths, void *stream) {
+  NEED_DEVICE();
+  return field_trace_paths(d_field, origin_cell, dims, d_starts, n_starts, max_cells, d_paths, d_lengths, S(stream));
+}
+
+int svoslam_workspace_plan_buffers(const svoslam_workspace *ws, void *d_ptrs[3], uint64_t bytes[3]) {
+  if (!ws || !d_ptrs || !bytes) return SVOSLAM_ERR_INVALID_ARG;
+  const svoslam::DeviceBuffer *slots[3] = {&ws->plan_bits, &ws->plan_weights, &ws->plan_ctl};
+  for (int k = 0; k < 3; k++) { d_ptrs[k] = slots[k]->ptr; bytes[k] = slots[k]->bytes; }
   return SVOSLAM_OK;
 }
 

@@ -41,16 +41,18 @@ int region_transform(const RegionPlan &p, int R, const unsigned long long *bits,
 // is then overwritten with *none
 int region_pack(const RegionPlan &own, int32_t *values, bool invert, const int *none, unsigned long long *bits, hipStream_t stream);
 
-// pool_distance_field first, then the caller's own two slots: what this call grew of the five does not stay behind a failure
+// pool_distance_field first, then the caller's own two or three slots: what this call grew of them does not stay behind a failure
 struct SlotRollback {
-  DeviceBuffer *slots[5];
-  size_t had[5];
-  SlotRollback(svoslam_workspace *ws, DeviceBuffer *own_a, DeviceBuffer *own_b) : slots{&ws->field_bits, &ws->field_a, &ws->field_b, own_a, own_b} {
-    for (int k = 0; k < 5; k++) had[k] = slots[k]->bytes;
+  DeviceBuffer *slots[6];
+  size_t had[6];
+  int n;
+  SlotRollback(svoslam_workspace *ws, DeviceBuffer *own_a, DeviceBuffer *own_b, DeviceBuffer *own_c = nullptr)
+      : slots{&ws->field_bits, &ws->field_a, &ws->field_b, own_a, own_b, own_c}, n(own_c ? 6 : 5) {
+    for (int k = 0; k < n; k++) had[k] = slots[k]->bytes;
   }
   int undo(int rc, hipStream_t stream) {  // the field's launches have finished before their slots go
     (void)hipStreamSynchronize(stream);
-    for (int k = 0; k < 5; k++)
+    for (int k = 0; k < n; k++)
       if (slots[k]->bytes != had[k]) slots[k]->release();
     return rc;
   }

@@ -1,6 +1,7 @@
 // map_sweeps.hpp -- the sweeps of a 64 x 8 x 8 tile staged in LDS that the reach field's relaxation (map_reach.hip, kStep = 1: a
 // move costs a step) and the component labels' tile minimum (map_components.hip, kStep = 0) share.  Values only move between cells
-// whose bit is set; each sweep is exact along its axis.  Everything is named scalars: no per-lane array.
+// whose bit is set; each sweep is exact along its axis.  Everything is named scalars: no per-lane array.  The weighted forms below
+// them are the cost field's (map_plan.hip): a move costs the weight of the cell it enters.
 #pragma once
 #include "common.hpp"
 
@@ -38,6 +39,59 @@ __device__ __forceinline__ int sweep_column(int32_t *cells, const unsigned long 
     if ((words[c * kWordPitch] >> lane) & 1ull) {
       const int v = cells[c * kPitch];
       prev = min(v, prev + kStep);
+      if (prev < v) { cells[c * kPitch] = prev; lowered = 1; }
+    } else {
+      prev = kNone;
+    }
+  }
+  return lowered;
+}
+
+// The weighted forms (map_plan.hip): entering a cell costs its own weight wt >= 1, so a tile needs the weights of its own cells only.
+//
+// x: v the cell's cost ("none" = kNone where its bit of `tw` is clear or nothing has reached it), wt its weight (0 where the bit is
+// clear).  With P the inclusive and E = P - wt the exclusive prefix sum of the row's weights, going up the row s(q) = P(q) + min
+// over p <= q of the same run of (s(p) - P(p)), going down s(q) = min over p >= q of the run of (s(p) + E(p)) - E(q): two plain
+// minimum scans by the doubling and the run-mask test of sweep_row.  The term p = q is v itself, so the result never exceeds v, and
+// a term that starts from kNone gives kNone or more: with costs below kNone "none" stays "none".  64 weights of 16 bits sum to
+// less than 2^22, so kNone = 2^30 leaves room on both sides.
+__device__ __forceinline__ int sweep_row_weighted(int v, int wt, unsigned long long tw, int lane) {
+  int P = wt;  // the inclusive prefix sum of the weights, over all 64 lanes: only differences inside a run are used
+#pragma unroll
+  for (int k = 1; k < 64; k *= 2) {
+    const int u = __shfl_up(P, k);
+    if (lane >= k) P += u;
+  }
+  int a = v - P;
+#pragma unroll
+  for (int k = 1; k < 64; k *= 2) {  // from below: cells lane - k .. lane all set
+    const int u = __shfl_up(a, k);
+    const unsigned long long run = ((2ull << k) - 1ull) << (lane >= k ? lane - k : 0);
+    if (lane >= k && (tw & run) == run) a = min(a, u);
+  }
+  v = a + P;
+  const int E = P - wt;
+  int b = v + E;
+#pragma unroll
+  for (int k = 1; k < 64; k *= 2) {  // from above: cells lane .. lane + k
+    const int u = __shfl_down(b, k);
+    const unsigned long long run = ((2ull << k) - 1ull) << lane;
+    if (lane + k < 64 && (tw & run) == run) b = min(b, u);
+  }
+  return b - E;
+}
+
+// y or z: sweep_column with the cell's own weight, at weights[c * kWeightPitch], in place of kStep
+template <int kNone, int kPitch, int kWordPitch, int kWeightPitch, bool kUp>
+__device__ __forceinline__ int sweep_column_weighted(int32_t *cells, const unsigned long long *words, const uint16_t *weights, int lane,
+                                                     int prev) {
+  int lowered = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const int c = kUp ? i : 7 - i;
+    if ((words[c * kWordPitch] >> lane) & 1ull) {
+      const int v = cells[c * kPitch];
+      prev = min(v, prev + (int)weights[c * kWeightPitch]);
       if (prev < v) { cells[c * kPitch] = prev; lowered = 1; }
     } else {
       prev = kNone;

@@ -1,0 +1,85 @@
+"""Paths through a box of a saved map (svoslam_pool_save checkpoint) that keep away from obstacles where they can, on one MI355X.
+
+    python tools/map_plan.py CHECKPOINT OUT.npz --box x0 y0 z0 x1 y1 z1 --clearance CELLS --comfort CELLS
+           (--penalty P | --ring-cost c1 c2 ...) --goal x y z --start x y z [--start ...] [--depth D]
+
+The box (metres, min xyz then max xyz) becomes the cell range svoslam_pool_count_boxes would count (svoslam_box_to_cells) at depth D
+(default: the map's stored depth), and the goal and every --start (metres) the cell that holds it, by the same rule.
+svoslam_pool_cost_field, seeded at the goal's cell, gives every cell of the box the cost of the cheapest path to the goal that stays
+in the box and at least --clearance cells clear of every occupied cell of the map: entering a cell costs 1, plus ring_cost[j -
+clearance - 1] when its nearest occupied cell is in ring j, (j - 1)^2 < squared distance <= j^2, clearance < j <= comfort.
+--ring-cost gives the comfort - clearance costs, nearest ring first; --penalty P is the linear ramp ring_cost[k] = P * (comfort -
+clearance - k).  svoslam_field_trace_paths then walks from every start down the field.  OUT.npz holds
+
+  cost[z, y, x]     int32, the cost to the goal; -1 = no path, -2 = blocked (an occupied cell within the clearance)
+  origin, dims      the first cell and the cells per axis (x, y, z) at `depth`
+  goal_cell         int32 [3], and start_cells int32 [n, 3] (a point outside the root cube: -1 -1 -1)
+  lengths, costs    int32 [n]: the cells of each start's path, start and goal included, and its cost (0 and -1: no path)
+  cells_K           int32 [lengths[K], 3], the cells of start K's path from the start to the goal
+  polyline_K        float64 [lengths[K], 3], their centres in metres
+  cell_size         metres per cell, and depth, center, edge_length, clearance_cells, comfort_cells, ring_cost, box, goal, starts
+
+Prints, per start, the cells and metres of its path and its cost."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("checkpoint")
+    ap.add_argument("out")
+    ap.add_argument("--box", type=float, nargs=6, required=True, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"), help="metres: min xyz, max xyz")
+    ap.add_argument("--clearance", type=int, required=True, help="cells every path keeps from occupied cells (0 .. 4096)")
+    ap.add_argument("--comfort", type=int, required=True, help="cells within which being near an occupied cell costs extra (clearance .. 4096)")
+    how = ap.add_mutually_exclusive_group(required=True)
+    how.add_argument("--penalty", type=int, help="linear ramp: ring k costs P * (comfort - clearance - k) extra")
+    how.add_argument("--ring-cost", type=int, nargs="*", help="comfort - clearance extra costs, nearest ring first (0 .. 65534 each)")
+    ap.add_argument("--goal", type=float, nargs=3, required=True, metavar=("X", "Y", "Z"), help="metres")
+    ap.add_argument("--start", type=float, nargs=3, action="append", required=True, metavar=("X", "Y", "Z"), help="metres; may be repeated")
+    ap.add_argument("--depth", type=int, default=None, help="lattice depth (default: the stored depth)")
+    args = ap.parse_args()
+    rings = args.comfort - args.clearance
+    if rings < 0:
+        sys.exit("--comfort is at least --clearance")
+    ring_cost = [args.penalty * (rings - k) for k in range(rings)] if args.penalty is not None else list(args.ring_cost)
+    if len(ring_cost) != rings:
+        sys.exit("--ring-cost takes comfort - clearance = %d values" % rings)
+    import svoslam_pkg
+    pkg = svoslam_pkg.load()
+    pool, ws = pkg.Pool(), pkg.Workspace()
+    center, edge, stored = pool.load(args.checkpoint)
+    depth = stored if args.depth is None else args.depth
+    plan = pkg.plan_paths(ws, pool, depth, center, edge, args.box, args.goal, args.start, args.clearance, args.comfort, ring_cost)
+    if plan is None:
+        sys.exit("the box is empty: a NaN, min > max, or outside the root cube")
+    none = np.full(3, -1, np.int32)
+    paths = plan["paths"]
+    out = dict(cost=plan["cost"], origin=plan["origin"].astype(np.int32), dims=plan["dims"].astype(np.int32),
+               goal_cell=none if plan["goal_cell"] is None else plan["goal_cell"],
+               start_cells=np.array([none if p["cell"] is None else p["cell"] for p in paths], np.int32).reshape(-1, 3),
+               lengths=np.array([p["length"] or 0 for p in paths], np.int32),
+               costs=np.array([-1 if p["cost"] is None else p["cost"] for p in paths], np.int32),
+               cell_size=plan["cell_size"], depth=depth, center=np.asarray(center, np.float32), edge_length=np.float32(edge),
+               clearance_cells=args.clearance, comfort_cells=args.comfort, ring_cost=np.array(ring_cost, np.int32),
+               box=np.asarray(args.box, np.float32), goal=np.asarray(args.goal, np.float32), starts=np.asarray(args.start, np.float32))
+    for k, p in enumerate(paths):
+        out["cells_%d" % k] = p["cells"] if p["cells"] is not None else np.zeros((0, 3), np.int32)
+        out["polyline_%d" % k] = p["polyline"] if p["polyline"] is not None else np.zeros((0, 3), np.float64)
+    np.savez_compressed(args.out, **out)
+    print("depth %d, cells %s + %s, clearance %d, comfort %d, ring cost %s -> %s" % (
+        depth, plan["origin"].tolist(), plan["dims"].tolist(), args.clearance, args.comfort, ring_cost, args.out))
+    for k, p in enumerate(paths):
+        if p["length"] is None:
+            print("start %d: no path" % k)
+        else:
+            print("start %d: %d cells, %.3f m, cost %d" % (k, p["length"], (p["length"] - 1) * plan["cell_size"], p["cost"]))
+
+
+if __name__ == "__main__":
+    main()
