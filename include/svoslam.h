@@ -804,6 +804,67 @@ int svoslam_field_trace_paths(const int32_t *d_field, const int32_t origin_cell[
  * the control record with the tile flags and the ring costs; NULL / 0 before the first call), as svoslam_workspace_reach_buffers
  * shows the reach field's.  Host only. */
 int svoslam_workspace_plan_buffers(const svoslam_workspace *ws, void *d_ptrs[3], uint64_t bytes[3]);
+/* Straightening planned paths (no reference counterpart; specification here and in DESIGN.md section 22): the clearance of straight
+ * segments over a distance field -- the trajectory check, and the first blocker of a line -- and the pruning of a chain of cells,
+ * such as svoslam_field_trace_paths writes, into a few vertices joined by straight segments that come no nearer to an obstacle
+ * than the stretch of the chain they replace did.  Exact, in integers.  No pool, no workspace; asynchronous on `stream`, nothing
+ * is read back; one SVOSLAM_STAGE_QUERY bracket around the one launch of each call.
+ *
+ * Common definitions
+ *   d_dist2: int32 in device memory, dims[0] * dims[1] * dims[2] values, x fastest, over the region origin_cell .. origin_cell +
+ *     dims, exactly as svoslam_pool_distance_field writes it: the squared distance in cells to the nearest occupied cell, -1 = none
+ *     within the field's radius.
+ *   g(c) = d_dist2[c] if that is >= 0, +infinity if it is -1, and 0 FOR A CELL OUTSIDE THE REGION (it counts as occupied).  No cell
+ *     outside the region is read.
+ *   C(a, b) for cells a and b: a, b and the supercover S(a, b) of svoslam_pool_visibility_field -- every other cell whose closed
+ *     cube meets the closed segment between the two centres; edges and corners count.
+ *   Walk order of C(a, b): a first; then the cells of S(a, b) crossing by crossing from a, where the segment passes through an edge
+ *     or a corner first the side cells of one axis in x, y, z order, then those of two axes (xy, xz, yz), then the diagonal cell;
+ *     b last.
+ *   Limits: at most 2^16 cells per axis of the region (every region of a root is within it; the bound under which the walk's
+ *     64-bit keys are proven, section 22) and at most 2^31 - 1 cells in all.
+ *
+ * svoslam_field_segment_clearance
+ *   d_segments: n rows of 6 int32 in device memory, a (x, y, z) then b (x, y, z), absolute cells.  a == b is allowed (C = {a}); an
+ *     end may lie outside the region, anywhere in int32: the minimum is then 0.
+ *   Outputs: d_min[i] = the minimum of g over C(a_i, b_i), -1 when that is +infinity; so 0 means "touches an occupied cell or
+ *     leaves the region".  d_at[i] (3 int32 per segment, may be NULL) = the first cell in walk order that attains the minimum,
+ *     absolute; a when every cell is +infinity.  One lane per segment; a walk ends early only when 0 was reached.
+ *   Errors: SVOSLAM_ERR_INVALID_ARG: NULL origin_cell or dims; a negative entry of dims or n; with n > 0 a NULL d_segments or d_min,
+ *     a NULL d_dist2 with a non-empty region.  SVOSLAM_ERR_POOL_LIMIT: the limits above.  n == 0 launches nothing.  A zero entry of
+ *     dims is valid: every cell has g = 0, d_min is 0 at a.
+ *
+ * svoslam_field_shorten_paths
+ *   d_paths, d_lengths, n_paths, max_cells: exactly svoslam_field_trace_paths' outputs.  Path i has L = min(|d_lengths[i]|,
+ *     max_cells) cells p_0 .. p_(L-1): a truncated path and a stopped (negative-length) one use their stored prefix.  The cells need
+ *     not be face neighbours and need not lie in the region: any list of cells is accepted.
+ *   r = clearance_cells, 0..SVOSLAM_MAX_RADIUS_CELLS.  THE CALLER MUST SUPPLY A FIELD WHOSE RADIUS IS >= r; the call cannot check it,
+ *     and on a field of a smaller radius cells nearer than r pass for clear.  W = max_lookahead >= 0, 0 = unlimited.
+ *   Rule: for a < j let m(a, j) = the minimum of g(p_i) over a <= i <= j.  The shortcut a -> j is admissible iff j == a + 1 (always,
+ *     whatever the cells are), or every c of C(p_a, p_j) has g(c) > r^2 and g(c) >= m(a, j): the segment keeps the clearance and
+ *     comes no nearer to an obstacle than the stretch it replaces was at its nearest.  The vertices are indices into the path: v_0
+ *     = 0, then v_(k+1) = the LARGEST admissible j with v_k < j <= min(L - 1, v_k + W) (no upper window for W = 0), until L - 1 is
+ *     reached.  Admissibility is not monotone in j; the whole window is examined.
+ *   Outputs: d_counts[i] = the number of vertices, EVEN WHEN IT EXCEEDS max_vertices; 0 for L = 0, 1 for L = 1.  d_vertices
+ *     [n_paths][max_vertices] int32 receives the first min(count, max_vertices) indices, the entries behind them are not written
+ *     (d_vertices may be NULL if max_vertices == 0).
+ *   With W = 1 every cell is a vertex.  On a field of radius r (every g > r^2 is +infinity) the rule is plain line-of-sight pruning
+ *     at clearance r; on a field of svoslam_pool_cost_field's comfort radius a path stays in the rings it was planned through.
+ *   Cost: one wavefront per path; with W = 0 a path of L cells takes O(L^2) walks in the worst case, W > 0 bounds it by L * W.
+ *   Errors: SVOSLAM_ERR_INVALID_ARG: NULL origin_cell or dims; a negative entry of dims, n_paths, max_cells, max_lookahead or
+ *     max_vertices; clearance_cells outside 0..SVOSLAM_MAX_RADIUS_CELLS; with n_paths > 0 a NULL d_lengths or d_counts, a NULL
+ *     d_dist2 with a non-empty region, a NULL d_paths with max_cells > 0, a NULL d_vertices with max_vertices > 0.
+ *     SVOSLAM_ERR_POOL_LIMIT: the limits above, n_paths * max_cells * 3 > 2^31 - 1, or n_paths * max_vertices > 2^31 - 1.  All are
+ *     decided before anything is written.  n_paths == 0 launches nothing.  A zero entry of dims is valid: every cell has g = 0, so
+ *     only the j == a + 1 steps remain. */
+int svoslam_field_segment_clearance(const int32_t *d_dist2, const int32_t origin_cell[3], const int32_t dims[3],
+                                    const int32_t *d_segments /* [n][6]: a xyz, b xyz */, int32_t n, int32_t *d_min /* [n] */,
+                                    int32_t *d_at /* [n][3], may be NULL */, void *stream);
+int svoslam_field_shorten_paths(const int32_t *d_dist2, const int32_t origin_cell[3], const int32_t dims[3], int32_t clearance_cells,
+                                const int32_t *d_paths /* [n_paths][max_cells][3] */, const int32_t *d_lengths /* [n_paths] */,
+                                int32_t n_paths, int32_t max_cells, int32_t max_lookahead, int32_t max_vertices,
+                                int32_t *d_vertices /* [n_paths][max_vertices], may be NULL if max_vertices == 0 */,
+                                int32_t *d_counts /* [n_paths] */, void *stream);
 /* The library's own sort and scan, exposed for tests and tools (no reference counterpart).  Every map operation sorts Morton keys
  * with the stable LSD radix sort of csrc/radix_sort.hip and compacts with its exclusive scan; these two calls reach them with
  * arguments of the caller's choosing, where the map's calls choose the form and the digit width from n.  All arrays are in device

@@ -231,6 +231,8 @@ SIGNATURES = {
                                           _i32, _vp, C.POINTER(_PlanStats), _vp]),
     "svoslam_field_trace_paths": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), _vp, _i32, _i32, _vp, _vp, _vp]),
     "svoslam_workspace_plan_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "svoslam_field_segment_clearance": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), _vp, _i32, _vp, _vp, _vp]),
+    "svoslam_field_shorten_paths": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "svoslam_sort_words": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "svoslam_exclusive_scan_u32": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp]),
     "svoslam_malloc": (C.c_int, [C.POINTER(_vp), C.c_size_t]),
@@ -1027,7 +1029,97 @@ def trace_paths(field, origin, dims, starts, max_cells, as_tensor=False):
     return paths.cpu().numpy(), lengths.cpu().numpy()
 
 
-def plan_paths(ws, pool, max_depth, center, edge_length, box, goal, starts, clearance_cells, comfort_cells, ring_cost, max_cells=None):
+def _field_tensor(field, n):
+    """a field over dims n, an array or an int32 cuda tensor -> a contiguous int32 cuda tensor"""
+    import torch
+    if isinstance(field, torch.Tensor):
+        if not field.is_cuda or field.dtype != torch.int32:
+            raise ValueError("a field tensor is int32 on the device")
+        t_field = field.contiguous()
+    else:
+        t_field = torch.from_numpy(np.ascontiguousarray(np.asarray(field, np.int32))).cuda()
+    if t_field.numel() != max(n[0], 0) * max(n[1], 0) * max(n[2], 0):
+        raise ValueError("the field holds dims[0] * dims[1] * dims[2] values")
+    return t_field
+
+
+def segment_clearance(field, origin, dims, segments, want_cell=False, as_tensor=False):
+    """svoslam_field_segment_clearance: for every segment ([n, 6] absolute cells, a xyz then b xyz: an array, or an int32 cuda
+    tensor) the smallest value of `field` (int32 [nz, ny, nx] over origin[3] .. origin + dims[3], as distance_field returns it: an
+    array or a cuda tensor) over a, the cells whose closed cube the centre-to-centre segment meets, and b; -1 counts as infinite
+    and a cell outside the region as 0.  -> int32 [n]: 0 = the segment touches an occupied cell or leaves the region, -1 = nothing
+    within the field's radius of it; with want_cell the pair (minimum, cells int32 [n, 3]): the first cell in walk order that
+    attains it.  numpy arrays, or with as_tensor cuda tensors and nothing is synchronised."""
+    import torch
+    o, n = [int(v) for v in origin], [int(v) for v in dims]
+    if len(o) != 3 or len(n) != 3:
+        raise ValueError("origin and dims are three cells each (x, y, z)")
+    t_field = _field_tensor(field, n)
+    if isinstance(segments, torch.Tensor):
+        if not segments.is_cuda or segments.dtype != torch.int32:
+            raise ValueError("a segments tensor is int32 on the device")
+        t_seg = segments.reshape(-1, 6).contiguous()
+    else:
+        t_seg = torch.from_numpy(np.ascontiguousarray(np.asarray(segments, np.int32).reshape(-1, 6))).cuda()
+    count = int(t_seg.shape[0])
+    low = torch.zeros(count, dtype=torch.int32, device="cuda")
+    at = torch.zeros((count, 3), dtype=torch.int32, device="cuda") if want_cell else None
+    check(lib().svoslam_field_segment_clearance(_ptr(t_field) if t_field.numel() else None, (_i32 * 3)(*o), (_i32 * 3)(*n),
+                                                _ptr(t_seg) if count else None, count, _ptr(low) if count else None,
+                                                _ptr(at) if want_cell and count else None, _stream()))
+    if not as_tensor:
+        low, at = low.cpu().numpy(), at.cpu().numpy() if want_cell else None
+    return (low, at) if want_cell else low
+
+
+def shorten_paths(field, origin, dims, clearance_cells, paths, lengths, max_lookahead=0, max_vertices=None, as_tensor=False):
+    """svoslam_field_shorten_paths: prune every path (paths int32 [n, max_cells, 3], lengths int32 [n], as trace_paths returns them:
+    arrays or cuda tensors) into vertices joined by straight segments.  From vertex a the next one is the largest j within
+    max_lookahead (0: unlimited) whose segment p_a .. p_j keeps more than clearance_cells from every occupied cell and comes no
+    nearer to one than the path between a and j did, by `field` (int32 [nz, ny, nx] as distance_field returns it, WITH A RADIUS >=
+    clearance_cells -- the call cannot check that); j = a + 1 always qualifies.  -> (vertices int32 [n, max_vertices], counts int32
+    [n]): indices into each path, counts[i] even beyond max_vertices, unwritten entries -1 here.  max_vertices=None: two passes,
+    the first for the counts alone (it blocks).  Unlimited lookahead costs O(length^2) segment walks per path in the worst case.
+    numpy arrays, or with as_tensor cuda tensors."""
+    import torch
+    o, n = [int(v) for v in origin], [int(v) for v in dims]
+    if len(o) != 3 or len(n) != 3:
+        raise ValueError("origin and dims are three cells each (x, y, z)")
+    t_field = _field_tensor(field, n)
+
+    def on_device(a, what):
+        if isinstance(a, torch.Tensor):
+            if not a.is_cuda or a.dtype != torch.int32:
+                raise ValueError("a %s tensor is int32 on the device" % what)
+            return a.contiguous()
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.int32))).cuda()
+    t_paths, t_lengths = on_device(paths, "paths"), on_device(lengths, "lengths").reshape(-1)
+    count = int(t_lengths.shape[0])
+    if t_paths.dim() != 3 or t_paths.shape[0] != count or t_paths.shape[2] != 3:
+        raise ValueError("paths is [n, max_cells, 3] for lengths [n]")
+    cap = int(t_paths.shape[1])
+
+    def run(room):
+        vertices = torch.full((count, max(room, 0)), -1, dtype=torch.int32, device="cuda")
+        counts = torch.zeros(count, dtype=torch.int32, device="cuda")
+        check(lib().svoslam_field_shorten_paths(_ptr(t_field) if t_field.numel() else None, (_i32 * 3)(*o), (_i32 * 3)(*n),
+                                                int(clearance_cells), _ptr(t_paths) if t_paths.numel() else None,
+                                                _ptr(t_lengths) if count else None, count, cap, int(max_lookahead), room,
+                                                _ptr(vertices) if vertices.numel() else None, _ptr(counts) if count else None,
+                                                _stream()))
+        return vertices, counts
+    if max_vertices is None:
+        _, counts = run(0)                                              # the counts alone: the room the longest result needs
+        vertices, counts = run(int(counts.max()) if count else 0)
+    else:
+        vertices, counts = run(int(max_vertices))
+    if as_tensor:
+        return vertices, counts
+    return vertices.cpu().numpy(), counts.cpu().numpy()
+
+
+def plan_paths(ws, pool, max_depth, center, edge_length, box, goal, starts, clearance_cells, comfort_cells, ring_cost, max_cells=None,
+               straighten=False, max_lookahead=0):
     """From every start to the goal (metres) through the box (metres: min xyz, max xyz) of the map, keeping clearance_cells from
     every occupied cell and paying ring_cost nearer than comfort_cells (cost_field).  The cells of the box are box_to_cells', the
     goal and the starts the cells that hold them by the same rule; the cost field is seeded at the goal's cell, computed once, and
@@ -1035,7 +1127,11 @@ def plan_paths(ws, pool, max_depth, center, edge_length, box, goal, starts, clea
     goal_cell (None outside the root cube), and paths, one dict per start: cell (None outside the root cube), cost and length (None
     without a path: the start or the goal is outside the box or blocked, or no path joins them), cells int32 [length, 3] from the
     start to the goal and polyline float64 [length, 3], their centres in metres (both None without a path).  max_cells: at most
-    that many cells of each path are kept (length still counts them all); default: every path whole."""
+    that many cells of each path are kept (length still counts them all); default: every path whole.  straighten: the kept cells
+    of every path are also pruned by shorten_paths against distance_field with radius comfort_cells, at clearance_cells and
+    max_lookahead (0: unlimited, O(length^2) segment walks per path in the worst case), and every path dict gains vertices (int32
+    indices into cells), waypoints (int32 [k, 3], the cells at them), waypoint_polyline (float64 [k, 3], metres) and
+    straight_length (the Euclidean length of that polyline in metres); all None without a path."""
     cells = box_to_cells(max_depth, center, edge_length, box)
     if cells is None:
         return None
@@ -1057,16 +1153,26 @@ def plan_paths(ws, pool, max_depth, center, edge_length, box, goal, starts, clea
     cell_size = 2.0 * float(edge_length) / (1 << int(max_depth))
     corner = np.asarray(center, np.float64) - float(edge_length)
     cost = cost.cpu().numpy()
+    if straighten:
+        comfort = distance_field(ws, pool, max_depth, lo, dims, comfort_cells, as_tensor=True)
+        vertices, counts = shorten_paths(comfort, lo, dims, clearance_cells, paths, lengths, max_lookahead=max_lookahead)
     out = []
     for k, c in enumerate(start_cells):
         n = int(lengths[k])
         if n <= 0:
             out.append(dict(cell=c, cost=None, length=None, cells=None, polyline=None))
+            if straighten:
+                out[-1].update(vertices=None, waypoints=None, waypoint_polyline=None, straight_length=None)
             continue
         kept = paths[k, :min(n, paths.shape[1])].copy()
         rel = c - lo
         out.append(dict(cell=c, cost=int(cost[rel[2], rel[1], rel[0]]), length=n, cells=kept,
                         polyline=corner + (kept.astype(np.float64) + 0.5) * cell_size))
+        if straighten:
+            at = vertices[k, :int(counts[k])].copy()
+            line = corner + (kept[at].astype(np.float64) + 0.5) * cell_size
+            out[-1].update(vertices=at, waypoints=kept[at], waypoint_polyline=line,
+                           straight_length=float(np.sqrt((np.diff(line, axis=0) ** 2).sum(1)).sum()))
     return dict(cost=cost, origin=lo, dims=dims, cell_size=cell_size, goal_cell=goal_cell, paths=out)
 
 

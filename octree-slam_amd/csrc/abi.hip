@@ -11,6 +11,7 @@
 #include "map_components.hpp"
 #include "map_field.hpp"
 #include "map_nearest.hpp"
+#include "map_paths.hpp"
 #include "map_plan.hpp"
 #include "map_query.hpp"
 #include "map_reach.hpp"
@@ -512,6 +513,20 @@ int svoslam_workspace_plan_buffers(const svoslam_workspace *ws, void *d_ptrs[3],
   const svoslam::DeviceBuffer *slots[3] = {&ws->plan_bits, &ws->plan_weights, &ws->plan_ctl};
   for (int k = 0; k < 3; k++) { d_ptrs[k] = slots[k]->ptr; bytes[k] = slots[k]->bytes; }
   return SVOSLAM_OK;
+}
+
+int svoslam_field_segment_clearance(const int32_t *d_dist2, const int32_t origin_cell[3], const int32_t dims[3],
+                                    const int32_t *d_segments, int32_t n, int32_t *d_min, int32_t *d_at, void *stream) {
+  NEED_DEVICE();
+  return field_segment_clearance(d_dist2, origin_cell, dims, d_segments, n, d_min, d_at, S(stream));
+}
+
+int svoslam_field_shorten_paths(const int32_t *d_dist2, const int32_t origin_cell[3], const int32_t dims[3], int32_t clearance_cells,
+                                const int32_t *d_paths, const int32_t *d_lengths, int32_t n_paths, int32_t max_cells,
+                                int32_t max_lookahead, int32_t max_vertices, int32_t *d_vertices, int32_t *d_counts, void *stream) {
+  NEED_DEVICE();
+  return field_shorten_paths(d_dist2, origin_cell, dims, clearance_cells, d_paths, d_lengths, n_paths, max_cells, max_lookahead,
+                             max_vertices, d_vertices, d_counts, S(stream));
 }
 
 // the library's own sort and scan with the caller's arguments (tests and tools)

@@ -2,6 +2,7 @@
 
     python tools/map_plan.py CHECKPOINT OUT.npz --box x0 y0 z0 x1 y1 z1 --clearance CELLS --comfort CELLS
            (--penalty P | --ring-cost c1 c2 ...) --goal x y z --start x y z [--start ...] [--depth D]
+           [--straighten [--lookahead K]]
 
 The box (metres, min xyz then max xyz) becomes the cell range svoslam_pool_count_boxes would count (svoslam_box_to_cells) at depth D
 (default: the map's stored depth), and the goal and every --start (metres) the cell that holds it, by the same rule.
@@ -19,7 +20,16 @@ clearance - k).  svoslam_field_trace_paths then walks from every start down the 
   polyline_K        float64 [lengths[K], 3], their centres in metres
   cell_size         metres per cell, and depth, center, edge_length, clearance_cells, comfort_cells, ring_cost, box, goal, starts
 
-Prints, per start, the cells and metres of its path and its cost."""
+With --straighten every path is also pruned by svoslam_field_shorten_paths into waypoints joined by straight segments that keep the
+clearance and come no nearer to an occupied cell than the stretch of the path they replace did, judged on the distance field with
+the comfort radius; --lookahead K looks at most K cells ahead of a waypoint (default 0: the whole path, which costs up to
+length^2 segment walks per path).  OUT.npz then also holds
+
+  vertices_K            int32 [k], indices into cells_K: the waypoints of start K's path, first and last cell included
+  waypoints_K           int32 [k, 3], the cells at them, and waypoint_polyline_K float64 [k, 3], their centres in metres
+  straight_lengths      float64 [n], the Euclidean length of each waypoint polyline in metres (0: no path), and lookahead
+
+Prints, per start, the cells and metres of its path and its cost, and with --straighten its waypoints and their metres."""
 import argparse
 import os
 import sys
@@ -43,7 +53,13 @@ def main():
     ap.add_argument("--goal", type=float, nargs=3, required=True, metavar=("X", "Y", "Z"), help="metres")
     ap.add_argument("--start", type=float, nargs=3, action="append", required=True, metavar=("X", "Y", "Z"), help="metres; may be repeated")
     ap.add_argument("--depth", type=int, default=None, help="lattice depth (default: the stored depth)")
+    ap.add_argument("--straighten", action="store_true", help="also prune every path into waypoints joined by straight segments")
+    ap.add_argument("--lookahead", type=int, default=0, help="with --straighten: cells a waypoint looks ahead (0: the whole path)")
     args = ap.parse_args()
+    if args.lookahead and not args.straighten:
+        sys.exit("--lookahead goes with --straighten")
+    if args.lookahead < 0:
+        sys.exit("--lookahead is 0 or more")
     rings = args.comfort - args.clearance
     if rings < 0:
         sys.exit("--comfort is at least --clearance")
@@ -55,7 +71,8 @@ def main():
     pool, ws = pkg.Pool(), pkg.Workspace()
     center, edge, stored = pool.load(args.checkpoint)
     depth = stored if args.depth is None else args.depth
-    plan = pkg.plan_paths(ws, pool, depth, center, edge, args.box, args.goal, args.start, args.clearance, args.comfort, ring_cost)
+    plan = pkg.plan_paths(ws, pool, depth, center, edge, args.box, args.goal, args.start, args.clearance, args.comfort, ring_cost,
+                          **(dict(straighten=True, max_lookahead=args.lookahead) if args.straighten else {}))
     if plan is None:
         sys.exit("the box is empty: a NaN, min > max, or outside the root cube")
     none = np.full(3, -1, np.int32)
@@ -71,6 +88,13 @@ def main():
     for k, p in enumerate(paths):
         out["cells_%d" % k] = p["cells"] if p["cells"] is not None else np.zeros((0, 3), np.int32)
         out["polyline_%d" % k] = p["polyline"] if p["polyline"] is not None else np.zeros((0, 3), np.float64)
+    if args.straighten:
+        out["lookahead"] = args.lookahead
+        out["straight_lengths"] = np.array([p["straight_length"] or 0.0 for p in paths], np.float64)
+        for k, p in enumerate(paths):
+            out["vertices_%d" % k] = p["vertices"] if p["vertices"] is not None else np.zeros(0, np.int32)
+            out["waypoints_%d" % k] = p["waypoints"] if p["waypoints"] is not None else np.zeros((0, 3), np.int32)
+            out["waypoint_polyline_%d" % k] = p["waypoint_polyline"] if p["waypoint_polyline"] is not None else np.zeros((0, 3), np.float64)
     np.savez_compressed(args.out, **out)
     print("depth %d, cells %s + %s, clearance %d, comfort %d, ring cost %s -> %s" % (
         depth, plan["origin"].tolist(), plan["dims"].tolist(), args.clearance, args.comfort, ring_cost, args.out))
@@ -79,6 +103,8 @@ def main():
             print("start %d: no path" % k)
         else:
             print("start %d: %d cells, %.3f m, cost %d" % (k, p["length"], (p["length"] - 1) * plan["cell_size"], p["cost"]))
+            if args.straighten:
+                print("start %d: %d waypoints, %.3f m" % (k, len(p["vertices"]), p["straight_length"]))
 
 
 if __name__ == "__main__":
