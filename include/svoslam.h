@@ -865,6 +865,82 @@ int svoslam_field_shorten_paths(const int32_t *d_dist2, const int32_t origin_cel
                                 int32_t n_paths, int32_t max_cells, int32_t max_lookahead, int32_t max_vertices,
                                 int32_t *d_vertices /* [n_paths][max_vertices], may be NULL if max_vertices == 0 */,
                                 int32_t *d_counts /* [n_paths] */, void *stream);
+/* Ground navigation in a map region (no reference counterpart; specification here and in DESIGN.md section 23): the cost-to-go
+ * field of a robot that stands on surfaces -- support under it, headroom above it, a body radius measured above the bumps it can
+ * roll over, a largest step it can climb and a price for climbing -- and the paths traced down it.  The ground counterpart of
+ * svoslam_pool_cost_field and svoslam_field_trace_paths.  Exact, in integers; the result does not depend on scheduling.
+ *
+ * svoslam_pool_ground_field
+ *   d, N, the occupied set O, the region and the output order are exactly those of svoslam_pool_distance_field.  Cells outside the
+ *     root are not occupied.
+ *   u: the unit cell vector of `up`: axis up >> 1 (1 = y, 2 = z), pointing to smaller coordinates if up & 1.  So 2 is +y (the
+ *     project's convention), 3 -y, 4 +z, 5 -z.  0 and 1, the x axis, are SVOSLAM_ERR_INVALID_ARG: the bit rows run along x.
+ *     "Horizontal" means the two axes other than u's; one of them is always x.
+ *   Parameters: r = radius_cells, 0..SVOSLAM_MAX_RADIUS_CELLS; H = height_cells, 1..SVOSLAM_MAX_HEIGHT_CELLS; S = step_cells,
+ *     0..min(H - 1, SVOSLAM_MAX_STEP_CELLS); c = climb_cost, 0..SVOSLAM_MAX_RING_COST; snap_cells, 0..SVOSLAM_MAX_SNAP_CELLS.
+ *   Foothold set G: a region cell q is a foothold iff (1) q - u is a cell of the root and is occupied; (2) for k = 0 .. H - 1 the
+ *     cell q + k u is not occupied; (3) for k = S .. H - 1 no occupied cell p exists that has the up-coordinate of q + k u and whose
+ *     horizontal squared distance to q is at most r^2.  Occupied cells outside the region count: up to r horizontally, up to H - 1
+ *     above and 1 below.  The body is a column of radius 0 up to the step height and a cylinder of radius r above it.  SUPPORT IS
+ *     ASKED OF THE CENTRE CELL ONLY: a foothold may overhang an edge by up to r cells.
+ *   Moves: from a foothold q to a foothold q + e + j u, e one of the four horizontal unit vectors, |j| <= S, both ends in the
+ *     region.  A move costs 1 + c |j|.  No move is vertical.
+ *   Seeds (d_seeds, n_seeds triples of int32 absolute cells, device memory): an entry outside the region is ignored.  Otherwise its
+ *     foothold is the first cell of G met going from the seed against u, the seed itself first, at most snap_cells further cells
+ *     examined, never leaving the region; an entry without one is ignored.
+ *   Output: d_cost, dims[0] * dims[1] * dims[2] values of type int32 in device memory, x fastest, indexed as d_dist2 is: -2 where q
+ *     is not in G, 0 at the foothold of a counted seed, otherwise the least total cost of a chain of moves from one, -1 without a
+ *     chain.  stats (may be NULL): footholds = |G| (a specified value); seeds_used = the entries that found a foothold, duplicates
+ *     each; rounds and tile_runs are diagnostics with no specified value.
+ *   Conventions: svoslam_pool_cost_field's -- any pool; pending asynchronous fusions are drained first; a deferred commit's pool is
+ *     read in its old state; THE CALL BLOCKS, the host reads one small record (32 bytes) per round; one SVOSLAM_STAGE_QUERY bracket;
+ *     the intermediates live in six grow-only slots of the workspace (svoslam_workspace_ground_buffers), so a second call of the
+ *     same size allocates nothing.
+ *   Errors: a zero entry of dims is SVOSLAM_OK and launches nothing, if the other arguments are valid.  SVOSLAM_ERR_INVALID_ARG: a
+ *     NULL ws, origin_cell or dims, max_depth outside 1..SVOSLAM_MAX_DEPTH, a region not inside the root, `up` outside 2..5, a
+ *     parameter outside its range above, n_seeds < 0 or NULL d_seeds with n_seeds > 0; with a non-empty region a NULL or
+ *     uninitialised pool or a NULL d_cost.  SVOSLAM_ERR_POOL_LIMIT, decided before anything is allocated or written: more than
+ *     2^31 - 1 cells, row words or elements of an intermediate of the region inflated by r horizontally, 1 below and H - 1 above;
+ *     more than 2^24 - 1 tiles of 64 x 8 x 8 cells; n_out * (1 + c * S) >= 2^30 (the value of "not reached").  SVOSLAM_ERR_OOM: an
+ *     allocation failed; the slots the call grew are released, after the stream has drained.  SVOSLAM_ERR_HIP with a text in
+ *     svoslam_last_error: the round cap (tiles * cells per tile + 1) was reached, which the argument of section 23 rules out.
+ *
+ * svoslam_field_trace_ground_paths (no pool, no workspace)
+ *   d_field: any int32 array in device memory laid out as d_cost over the region; -2 = not a foothold, -1 = a foothold that cannot
+ *     be reached, >= 0 a cost-to-go.  up, step_cells, climb_cost and snap_cells as above (step_cells 0..SVOSLAM_MAX_STEP_CELLS; no
+ *     height is needed).  d_starts: n_starts triples (x, y, z) of int32 absolute cells, in device memory.
+ *   Snapping: the foothold of a start is the first cell with a value other than -2, going from the start against u, the start itself
+ *     first, within snap_cells further cells, inside the region.  A start outside the region, without a foothold, or whose foothold
+ *     holds -1 has length 0 and stores nothing.
+ *   The walk begins at the foothold.  From a cell q of value v > 0 it moves to the FIRST candidate q' = q + e + j u inside the region
+ *     whose value v' satisfies v' >= 0 and v' + 1 + c |j| == v.  Candidates are ordered by e first -- minus then plus along x, then
+ *     minus and plus along the other horizontal axis -- and within one e by j = 0, -1, +1, -2, +2, ... up to |j| = S.  (The smallest
+ *     neighbour value alone is not a predecessor here: moves into one cell differ in price.)  The walk ends at value 0.  If no
+ *     candidate qualifies it stops, and the length is MINUS the number of cells walked.  The values fall strictly, so the walk is
+ *     bounded by its data.
+ *   Outputs: d_paths and d_lengths exactly as svoslam_field_trace_paths writes them: the length counts the whole path even beyond
+ *     max_cells, nothing behind the stored cells is written.  Asynchronous on `stream`, nothing is read back; one
+ *     SVOSLAM_STAGE_QUERY bracket.
+ *   Errors: those of svoslam_field_trace_paths, and SVOSLAM_ERR_INVALID_ARG for `up` outside 2..5, step_cells, climb_cost or
+ *     snap_cells outside their ranges. */
+#define SVOSLAM_MAX_STEP_CELLS 4
+#define SVOSLAM_MAX_HEIGHT_CELLS 256
+#define SVOSLAM_MAX_SNAP_CELLS 256
+typedef struct { int32_t footholds, seeds_used, rounds, tile_runs; } svoslam_ground_stats;
+int svoslam_pool_ground_field(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                              const int32_t dims[3], int32_t up /* 2 +y, 3 -y, 4 +z, 5 -z */, int32_t radius_cells,
+                              int32_t height_cells, int32_t step_cells, int32_t climb_cost, int32_t snap_cells, const int32_t *d_seeds,
+                              int32_t n_seeds, int32_t *d_cost, svoslam_ground_stats *stats /* may be NULL */, void *stream);
+int svoslam_field_trace_ground_paths(const int32_t *d_field, const int32_t origin_cell[3], const int32_t dims[3], int32_t up,
+                                     int32_t step_cells, int32_t climb_cost, int32_t snap_cells, const int32_t *d_starts,
+                                     int32_t n_starts, int32_t max_cells,
+                                     int32_t *d_paths /* [n_starts][max_cells][3], may be NULL if max_cells == 0 */,
+                                     int32_t *d_lengths /* [n_starts] */, void *stream);
+/* diagnostics: the device pointers and sizes in bytes of the workspace's six ground-field slots (the occupancy bit rows of the
+ * inflated region; the planar transform's values after its x pass; after its second pass; the body bit rows D; the foothold bit
+ * rows G; the control record with the tile flags; NULL / 0 before the first call that needs them), as
+ * svoslam_workspace_plan_buffers shows the cost field's.  Host only. */
+int svoslam_workspace_ground_buffers(const svoslam_workspace *ws, void *d_ptrs[6], uint64_t bytes[6]);
 /* The library's own sort and scan, exposed for tests and tools (no reference counterpart).  Every map operation sorts Morton keys
  * with the stable LSD radix sort of csrc/radix_sort.hip and compacts with its exclusive scan; these two calls reach them with
  * arguments of the caller's choosing, where the map's calls choose the form and the digit width from n.  All arrays are in device

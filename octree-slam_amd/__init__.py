@@ -54,6 +54,10 @@ class _PlanStats(C.Structure):
     _fields_ = [("rounds", C.c_int32), ("tile_runs", C.c_int32), ("seeds_used", C.c_int32), ("max_weight", C.c_int32)]
 
 
+class _GroundStats(C.Structure):
+    _fields_ = [("footholds", C.c_int32), ("seeds_used", C.c_int32), ("rounds", C.c_int32), ("tile_runs", C.c_int32)]
+
+
 class _ComponentStats(C.Structure):
     _fields_ = [("components", C.c_int32), ("largest", C.c_int32), ("tile_passes", C.c_int32), ("unions", C.c_int32)]
 
@@ -233,6 +237,11 @@ SIGNATURES = {
     "svoslam_workspace_plan_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
     "svoslam_field_segment_clearance": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), _vp, _i32, _vp, _vp, _vp]),
     "svoslam_field_shorten_paths": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "svoslam_pool_ground_field": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32,
+                                            _i32, _vp, _i32, _vp, C.POINTER(_GroundStats), _vp]),
+    "svoslam_field_trace_ground_paths": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp,
+                                                   _vp]),
+    "svoslam_workspace_ground_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
     "svoslam_sort_words": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "svoslam_exclusive_scan_u32": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp]),
     "svoslam_malloc": (C.c_int, [C.POINTER(_vp), C.c_size_t]),
@@ -416,6 +425,12 @@ class Workspace:
         ptrs, sizes = (_vp * 3)(), (C.c_uint64 * 3)()
         check(lib().svoslam_workspace_plan_buffers(self._h, ptrs, sizes))
         return [(int(ptrs[k] or 0), int(sizes[k])) for k in range(3)]
+
+    def ground_buffers(self):
+        """svoslam_workspace_ground_buffers: [(device pointer, bytes)] of the six ground-field slots (diagnostics)"""
+        ptrs, sizes = (_vp * 6)(), (C.c_uint64 * 6)()
+        check(lib().svoslam_workspace_ground_buffers(self._h, ptrs, sizes))
+        return [(int(ptrs[k] or 0), int(sizes[k])) for k in range(6)]
 
     def component_buffers(self):
         """svoslam_workspace_component_buffers: [(device pointer, bytes)] of the two component slots (diagnostics)"""
@@ -1174,6 +1189,126 @@ def plan_paths(ws, pool, max_depth, center, edge_length, box, goal, starts, clea
             out[-1].update(vertices=at, waypoints=kept[at], waypoint_polyline=line,
                            straight_length=float(np.sqrt((np.diff(line, axis=0) ** 2).sum(1)).sum()))
     return dict(cost=cost, origin=lo, dims=dims, cell_size=cell_size, goal_cell=goal_cell, paths=out)
+
+
+UP_PLUS_Y, UP_MINUS_Y, UP_PLUS_Z, UP_MINUS_Z = 2, 3, 4, 5                # include/svoslam.h: the `up` of the ground calls
+MAX_STEP_CELLS, MAX_HEIGHT_CELLS, MAX_SNAP_CELLS = 4, 256, 256          # include/svoslam.h SVOSLAM_MAX_{STEP,HEIGHT,SNAP}_CELLS
+_UP_NAMES = {"+y": 2, "-y": 3, "+z": 4, "-z": 5}
+
+
+def _up_code(up):
+    """2..5, or one of "+y", "-y", "+z", "-z" -> the integer the library takes (another integer goes through for it to refuse)"""
+    if isinstance(up, str):
+        if up not in _UP_NAMES:
+            raise ValueError("up is one of %s, or 2 .. 5" % ", ".join(sorted(_UP_NAMES)))
+        return _UP_NAMES[up]
+    return int(up)
+
+
+def ground_field(ws, pool, max_depth, origin, dims, up, radius_cells, height_cells, step_cells, climb_cost, seeds, snap_cells=0,
+                 as_tensor=False, stats=None):
+    """svoslam_pool_ground_field: the cost-to-go field of a robot that stands on surfaces, over the region origin[3] .. origin +
+    dims[3] (cells at max_depth, x y z).  `up`: 2 or "+y" (the project's convention), 3 "-y", 4 "+z", 5 "-z".  A cell is a foothold
+    iff the cell under it is occupied, height_cells cells from it upwards are free, and from step_cells above it upwards no occupied
+    cell of the same layer lies within radius_cells horizontally.  A move goes one cell horizontally and at most step_cells (<=
+    min(height_cells - 1, MAX_STEP_CELLS)) up or down, between footholds in the region, and costs 1 + climb_cost * cells climbed.
+    `seeds` ([n, 3] absolute cells: an array, or an int32 cuda tensor) are snapped downwards by at most snap_cells to their
+    foothold.  -> int32 [nz, ny, nx]: 0 at a counted seed's foothold, the cheapest chain of moves from one elsewhere, -1 without a
+    chain, -2 where the cell is no foothold; a numpy array, or with as_tensor a cuda tensor.  The call blocks either way.  `stats`:
+    a dict that receives footholds, seeds_used, rounds and tile_runs."""
+    import torch
+    o, n = [int(v) for v in origin], [int(v) for v in dims]
+    if len(o) != 3 or len(n) != 3:
+        raise ValueError("origin and dims are three cells each (x, y, z)")
+    t_seeds = _cells_tensor(seeds, "seeds")
+    count = int(t_seeds.shape[0])
+    out = torch.empty([max(v, 0) for v in reversed(n)], dtype=torch.int32, device="cuda")
+    st = _GroundStats()
+    check(lib().svoslam_pool_ground_field(ws._h, C.byref(pool._p), int(max_depth), (_i32 * 3)(*o), (_i32 * 3)(*n), _up_code(up),
+                                          int(radius_cells), int(height_cells), int(step_cells), int(climb_cost), int(snap_cells),
+                                          _ptr(t_seeds) if count else None, count, _ptr(out), C.byref(st), _stream()))
+    if stats is not None:
+        stats.update(footholds=int(st.footholds), seeds_used=int(st.seeds_used), rounds=int(st.rounds), tile_runs=int(st.tile_runs))
+    return out if as_tensor else out.cpu().numpy()
+
+
+def trace_ground_paths(field, origin, dims, up, step_cells, climb_cost, starts, max_cells, snap_cells=0, as_tensor=False):
+    """svoslam_field_trace_ground_paths: from every start ([n, 3] absolute cells: an array, or an int32 cuda tensor), snapped
+    downwards by at most snap_cells to the first cell whose value is not -2, down `field` (int32 [nz, ny, nx] over origin[3] ..
+    origin + dims[3], as ground_field returns it with the same up, step_cells and climb_cost: an array or a cuda tensor): from a
+    cell of value v > 0 to the first cell one step away horizontally and j cells up or down whose value v' >= 0 has v' + 1 +
+    climb_cost * |j| == v, the horizontal directions in the order -x, +x, then - and + along the other horizontal axis, and j = 0,
+    -1, +1, -2, +2, ... within each; until a cell of value 0.  -> (paths int32 [n, max_cells, 3], lengths int32 [n]) as trace_paths
+    returns them: lengths[i] counts the whole path even beyond max_cells, unwritten rows are -1 here, length 0 = no foothold under
+    the start or no way from it, a negative length = not such a field.  numpy arrays, or with as_tensor cuda tensors and nothing is
+    synchronised."""
+    import torch
+    o, n = [int(v) for v in origin], [int(v) for v in dims]
+    if len(o) != 3 or len(n) != 3:
+        raise ValueError("origin and dims are three cells each (x, y, z)")
+    t_field = _field_tensor(field, n)
+    t_starts = _cells_tensor(starts, "starts")
+    count, cap = int(t_starts.shape[0]), int(max_cells)
+    paths = torch.full((count, max(cap, 0), 3), -1, dtype=torch.int32, device="cuda")
+    lengths = torch.zeros(count, dtype=torch.int32, device="cuda")
+    check(lib().svoslam_field_trace_ground_paths(_ptr(t_field) if t_field.numel() else None, (_i32 * 3)(*o), (_i32 * 3)(*n), _up_code(up),
+                                                 int(step_cells), int(climb_cost), int(snap_cells), _ptr(t_starts) if count else None,
+                                                 count, cap, _ptr(paths) if paths.numel() else None,
+                                                 _ptr(lengths) if count else None, _stream()))
+    if as_tensor:
+        return paths, lengths
+    return paths.cpu().numpy(), lengths.cpu().numpy()
+
+
+def plan_ground_paths(ws, pool, max_depth, center, edge_length, box, goal, starts, up, radius_cells, height_cells, step_cells, climb_cost,
+                      snap_cells, max_cells=None):
+    """From every start to the goal (metres) over the ground of the box (metres: min xyz, max xyz) of the map, for a robot of
+    radius_cells and height_cells that climbs step_cells at climb_cost a cell (ground_field).  Shaped as plan_paths: the cells of
+    the box are box_to_cells', the goal and the starts the cells that hold them, each snapped downwards by at most snap_cells to
+    its foothold; the field is seeded at the goal, computed once, and every start is traced down it (trace_ground_paths) twice,
+    for the lengths and then for the cells.  -> None for an empty box, else a dict: cost (the field), origin, dims, cell_size,
+    goal_cell (None outside the root cube), footholds, and paths, one dict per start: cell (None outside the root cube), cost,
+    length and climb (None without a path), cells int32 [length, 3] from the start's foothold to the goal's and polyline float64
+    [length, 3], their centres in metres (both None without a path); climb is the total of cells climbed or descended.  max_cells:
+    at most that many cells of each path are kept (length still counts them all; climb then covers the kept cells)."""
+    cells = box_to_cells(max_depth, center, edge_length, box)
+    if cells is None:
+        return None
+    lo, hi = cells
+    dims = hi - lo + 1
+    code = _up_code(up)
+
+    def cell_of(point):
+        at = box_to_cells(max_depth, center, edge_length, [float(v) for v in point] * 2)
+        return None if at is None else at[0]
+    goal_cell = cell_of(goal)
+    start_cells = [cell_of(s) for s in np.asarray(starts, np.float64).reshape(-1, 3)]
+    outside = lo - 1                                                    # a cell that is not in the region, for points outside the root
+    stats = {}
+    cost = ground_field(ws, pool, max_depth, lo, dims, code, radius_cells, height_cells, step_cells, climb_cost,
+                        [goal_cell if goal_cell is not None else outside], snap_cells=snap_cells, as_tensor=True, stats=stats)
+    stand_ins = [c if c is not None else outside for c in start_cells]
+    _, lengths = trace_ground_paths(cost, lo, dims, code, step_cells, climb_cost, stand_ins, 0, snap_cells=snap_cells)
+    room = int(lengths.max()) if len(stand_ins) else 0
+    paths, lengths = trace_ground_paths(cost, lo, dims, code, step_cells, climb_cost, stand_ins,
+                                        room if max_cells is None else min(room, int(max_cells)), snap_cells=snap_cells)
+    cell_size = 2.0 * float(edge_length) / (1 << int(max_depth))
+    corner = np.asarray(center, np.float64) - float(edge_length)
+    cost = cost.cpu().numpy()
+    out = []
+    for k, c in enumerate(start_cells):
+        n = int(lengths[k])
+        if n <= 0:
+            out.append(dict(cell=c, cost=None, length=None, climb=None, cells=None, polyline=None))
+            continue
+        kept = paths[k, :min(n, paths.shape[1])].copy()
+        value = None
+        if len(kept):
+            rel = kept[0] - lo
+            value = int(cost[rel[2], rel[1], rel[0]])
+        out.append(dict(cell=c, cost=value, length=n, climb=int(np.abs(np.diff(kept[:, code >> 1])).sum()), cells=kept,
+                        polyline=corner + (kept.astype(np.float64) + 0.5) * cell_size))
+    return dict(cost=cost, origin=lo, dims=dims, cell_size=cell_size, goal_cell=goal_cell, footholds=stats["footholds"], paths=out)
 
 
 COMPONENTS_FREE, COMPONENTS_SOLID = 0, 1                                # include/svoslam.h SVOSLAM_COMPONENTS_*

@@ -10,6 +10,7 @@
 #include "image_kernels.hpp"
 #include "map_components.hpp"
 #include "map_field.hpp"
+#include "map_ground.hpp"
 #include "map_nearest.hpp"
 #include "map_paths.hpp"
 #include "map_plan.hpp"
@@ -527,6 +528,31 @@ int svoslam_field_shorten_paths(const int32_t *d_dist2, const int32_t origin_cel
   NEED_DEVICE();
   return field_shorten_paths(d_dist2, origin_cell, dims, clearance_cells, d_paths, d_lengths, n_paths, max_cells, max_lookahead,
                              max_vertices, d_vertices, d_counts, S(stream));
+}
+
+int svoslam_pool_ground_field(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                              const int32_t dims[3], int32_t up, int32_t radius_cells, int32_t height_cells, int32_t step_cells,
+                              int32_t climb_cost, int32_t snap_cells, const int32_t *d_seeds, int32_t n_seeds, int32_t *d_cost,
+                              svoslam_ground_stats *stats, void *stream) {
+  NEED_DEVICE();
+  return pool_ground_field(ws, pool, max_depth, origin_cell, dims, up, radius_cells, height_cells, step_cells, climb_cost, snap_cells,
+                           d_seeds, n_seeds, d_cost, stats, S(stream));
+}
+
+int svoslam_field_trace_ground_paths(const int32_t *d_field, const int32_t origin_cell[3], const int32_t dims[3], int32_t up,
+                                     int32_t step_cells, int32_t climb_cost, int32_t snap_cells, const int32_t *d_starts,
+                                     int32_t n_starts, int32_t max_cells, int32_t *d_paths, int32_t *d_lengths, void *stream) {
+  NEED_DEVICE();
+  return field_trace_ground_paths(d_field, origin_cell, dims, up, step_cells, climb_cost, snap_cells, d_starts, n_starts, max_cells,
+                                  d_paths, d_lengths, S(stream));
+}
+
+int svoslam_workspace_ground_buffers(const svoslam_workspace *ws, void *d_ptrs[6], uint64_t bytes[6]) {
+  if (!ws || !d_ptrs || !bytes) return SVOSLAM_ERR_INVALID_ARG;
+  const svoslam::DeviceBuffer *slots[6] = {&ws->ground_bits, &ws->ground_a,    &ws->ground_b,
+                                           &ws->ground_body, &ws->ground_foot, &ws->ground_ctl};
+  for (int k = 0; k < 6; k++) { d_ptrs[k] = slots[k]->ptr; bytes[k] = slots[k]->bytes; }
+  return SVOSLAM_OK;
 }
 
 // the library's own sort and scan with the caller's arguments (tests and tools)

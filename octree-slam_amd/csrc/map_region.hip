@@ -36,6 +36,9 @@
 //                         one wavefront per 64 consecutive x of a row of the region itself: the ballot of (value == -1) != invert
 //                         is the row word (the raster's layout), written by lane 0 with one vector store; kOverwrite: every lane
 //                         then overwrites its own value with the caller's "none", so the array becomes a working array in place.
+// The ground field (map_ground.hip, section 23) plans with an inflation per axis and side (plan_region_axes) and transforms within
+// the layers of its up axis only (region_transform_planar): edt_x_kernel<false> and one edt_pass_kernel along the other horizontal
+// axis, the same kernels launched with that axis' strides; the pass along up is left out.
 // Which path: R <= kLdsMaxRadius (64) stages in LDS, (64 + 2 R) * 256 bytes per workgroup, 48 KB at most; a larger R runs the
 // same kernel reading the intermediate from global memory (kLds = false): the same search, no staging.  The host decides from R
 // alone.
@@ -242,6 +245,37 @@ int plan_region(int depth, const int32_t origin[3], const int32_t dims[3], int R
   return SVOSLAM_OK;
 }
 
+int plan_region_axes(int depth, const int32_t origin[3], const int32_t dims[3], const int below[3], const int above[3], int pass_axis,
+                     RegionPlan *plan) {
+  if (!origin || !dims || depth < 1 || depth > SVOSLAM_MAX_DEPTH || (pass_axis != 1 && pass_axis != 2)) return SVOSLAM_ERR_INVALID_ARG;
+  RegionPlan &p = *plan;
+  const long long N = 1ll << depth;
+  p.nothing = false;
+  for (int a = 0; a < 3; a++) {
+    if (below[a] < 0 || below[a] > SVOSLAM_MAX_RADIUS_CELLS || above[a] < 0 || above[a] > SVOSLAM_MAX_RADIUS_CELLS)
+      return SVOSLAM_ERR_INVALID_ARG;
+    if (dims[a] < 0 || origin[a] < 0 || (long long)origin[a] + dims[a] > N) return SVOSLAM_ERR_INVALID_ARG;
+    p.nothing = p.nothing || dims[a] == 0;
+    p.lo[a] = origin[a] - below[a] > 0 ? origin[a] - below[a] : 0;
+    const long long end = (long long)origin[a] + dims[a] + above[a] < N ? (long long)origin[a] + dims[a] + above[a] : N;
+    p.len[a] = end - p.lo[a];
+    p.off[a] = (int)(origin[a] - p.lo[a]);
+  }
+  p.nx = dims[0], p.ny = dims[1], p.nz = dims[2];
+  p.n_out = p.nx * p.ny * p.nz;
+  p.wpr = (p.len[0] + 63) / 64;
+  p.words = p.wpr * p.len[1] * p.len[2];
+  p.n_g1 = p.nx * p.len[1] * p.len[2];
+  p.n_g2 = pass_axis == 1 ? p.nx * p.ny * p.len[2] : p.nx * p.len[1] * p.nz;
+  return SVOSLAM_OK;
+}
+
+bool planar_within_limits(const RegionPlan &p, int pass_axis) {
+  const long long limit = INT_MAX, xtiles = (p.nx + 63) / 64;
+  const long long blocks = pass_axis == 1 ? xtiles * p.len[2] * ((p.ny + kSeg - 1) / kSeg) : xtiles * p.len[1] * ((p.nz + kSeg - 1) / kSeg);
+  return p.words <= limit && p.n_g1 <= limit && p.n_g2 <= limit && blocks <= limit;
+}
+
 int admit_region(const char *fn, const svoslam_pool *pool, const RegionPlan &p, int R, bool transform, hipStream_t stream) {
   if (!pool || !pool->d_data) return SVOSLAM_ERR_INVALID_ARG;
   const long long limit = INT_MAX, xtiles = (p.nx + 63) / 64;
@@ -286,6 +320,17 @@ int region_transform(const RegionPlan &p, int R, const unsigned long long *bits,
                      uint16_t *ay, uint16_t *az, hipStream_t stream, LaunchEvents *timed) {
   return wx ? transform<true>(p, R, bits, g1, g2, out, wx, ay, az, stream, timed)
             : transform<false>(p, R, bits, g1, g2, out, nullptr, nullptr, nullptr, stream, timed);
+}
+
+int region_transform_planar(const RegionPlan &p, int R, int pass_axis, const unsigned long long *bits, int32_t *g1, int32_t *out,
+                            hipStream_t stream) {
+  const long long nx = p.nx, ly = p.len[1];
+  edt_x_kernel<false><<<cdiv(p.n_g1, 256), 256, 0, stream>>>(bits, (int)p.wpr, (int)nx, p.off[0], R, p.n_g1, g1, nullptr);
+  SVO_LAUNCH_CHECK();
+  if (pass_axis == 1)  // y: columns (z of the inflated range, x), g1[z'][y'][x] -> out[z'][y][x]
+    return launch_pass<false>(g1, nx, p.len[2], ly, p.ny, p.off[1], nx, ly * nx, nx, p.ny * nx, R, -1, out, nullptr, stream);
+  // z: columns (y of the inflated range, x), g1[z'][y'][x] -> out[z][y'][x]
+  return launch_pass<false>(g1, nx, ly, p.len[2], p.nz, p.off[2], ly * nx, nx, ly * nx, nx, R, -1, out, nullptr, stream);
 }
 
 int region_pack(const RegionPlan &own, int32_t *values, bool invert, const int *none, unsigned long long *bits, hipStream_t stream) {

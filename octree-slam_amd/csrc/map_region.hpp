@@ -17,6 +17,12 @@ struct RegionPlan {
 
 // SVOSLAM_ERR_INVALID_ARG unless 1 <= depth <= SVOSLAM_MAX_DEPTH, 0 <= R <= SVOSLAM_MAX_RADIUS_CELLS and the region lies in the root
 int plan_region(int depth, const int32_t origin[3], const int32_t dims[3], int R, RegionPlan *plan);
+// the same with an inflation per axis and side: `below[a]` cells towards smaller and `above[a]` towards larger coordinates, each in
+// 0..SVOSLAM_MAX_RADIUS_CELLS.  n_g1 and n_g2 are those of region_transform_planar along `pass_axis` (1 or 2): the axis other than
+// x and pass_axis is not transformed and keeps its inflated length -- g1 [len z][len y][nx], g2 the same with pass_axis cut to the
+// region
+int plan_region_axes(int depth, const int32_t origin[3], const int32_t dims[3], const int below[3], const int above[3], int pass_axis,
+                     RegionPlan *plan);
 // what follows a caller's own argument checks: the pool, the 2^31 - 1 limits (worded for the public function `fn`; `transform`:
 // those of region_transform's intermediates too), then the drain of pending asynchronous fusions
 int admit_region(const char *fn, const svoslam_pool *pool, const RegionPlan &p, int R, bool transform, hipStream_t stream);
@@ -36,6 +42,13 @@ struct LaunchEvents {  // the profiling form's events: mark() in front of each l
 // where its minimum lies, the smallest index among the equally near: wx[p.n_g1], ay[p.n_g2], az[p.n_out]; else all three are NULL
 int region_transform(const RegionPlan &p, int R, const unsigned long long *bits, int32_t *g1, int32_t *g2, int32_t *out, uint16_t *wx,
                      uint16_t *ay, uint16_t *az, hipStream_t stream, LaunchEvents *timed = nullptr);
+
+// the planar transform of a plan_region_axes plan: edt_x_kernel, then one column pass along pass_axis; the third axis is left alone,
+// so out[p.n_g2] holds, per layer of that axis, the squared distance within the layer (-1: nothing within R)
+int region_transform_planar(const RegionPlan &p, int R, int pass_axis, const unsigned long long *bits, int32_t *g1, int32_t *out,
+                            hipStream_t stream);
+// the 2^31 - 1 limits of region_transform_planar's intermediates and launches
+bool planar_within_limits(const RegionPlan &p, int pass_axis);
 
 // `own`: the plan of the region with R = 0.  bits[own.words]: bit x of a row = (values == -1) != invert; with `none`, every value
 // is then overwritten with *none

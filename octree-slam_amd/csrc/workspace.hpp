@@ -57,6 +57,8 @@ struct svoslam_workspace {
   svoslam::DeviceBuffer field_bits, field_a, field_b;     // distance field: occupancy bit rows of the inflated region; after the x pass; after the y pass
   svoslam::DeviceBuffer reach_bits, reach_flags;          // reach field: traversable bit rows of the region; control record + the tile flags of two rounds
   svoslam::DeviceBuffer plan_bits, plan_weights, plan_ctl;  // cost field: traversable bit rows of the region; a 16-bit weight per cell; control record + the tile flags of two rounds + the ring costs
+  svoslam::DeviceBuffer ground_bits, ground_a, ground_b;  // ground field: occupancy bit rows of the inflated region; the planar transform after its x pass; after its second pass
+  svoslam::DeviceBuffer ground_body, ground_foot, ground_ctl;  // ... the body bit rows D; the foothold bit rows G of the region; control record + the tile flags of two rounds
   svoslam::DeviceBuffer comp_bits, comp_ctl;              // component labels: bit rows of the set on the region; the 32-byte control record
   svoslam::DeviceBuffer near_bits, near_dist, near_arg;   // nearest-cell field: target bit rows of the inflated region; the values after the x, y and z pass; the three passes' 16-bit indices
   svoslam::DeviceBuffer vis_bits;                         // visibility field: occupancy bit rows of the region inflated by the range
@@ -88,7 +90,7 @@ struct svoslam_workspace {
     leaf_t.release(); leaf_f.release(); rec_key.release(); rec_front.release(); path_nodes.release(); strad.release();
     rec_pass.release(); apply_nodes.release(); leaf_rec0.release(); leaf_start.release();
     kr_keys.release(); kr_idx.release(); kr_small.release();
-    bfs_a.release(); bfs_b.release(); bfs_mask.release(); bfs_ptr.release(); surf_color.release(); surf_tiles.release(); field_bits.release(); field_a.release(); field_b.release(); reach_bits.release(); reach_flags.release(); plan_bits.release(); plan_weights.release(); plan_ctl.release(); comp_bits.release(); comp_ctl.release(); near_bits.release(); near_dist.release(); near_arg.release(); vis_bits.release(); score_rec.release(); misc.release(); scan_tmp.release(); frame_bbox.release();
+    bfs_a.release(); bfs_b.release(); bfs_mask.release(); bfs_ptr.release(); surf_color.release(); surf_tiles.release(); field_bits.release(); field_a.release(); field_b.release(); reach_bits.release(); reach_flags.release(); plan_bits.release(); plan_weights.release(); plan_ctl.release(); ground_bits.release(); ground_a.release(); ground_b.release(); ground_body.release(); ground_foot.release(); ground_ctl.release(); comp_bits.release(); comp_ctl.release(); near_bits.release(); near_dist.release(); near_arg.release(); vis_bits.release(); score_rec.release(); misc.release(); scan_tmp.release(); frame_bbox.release();
     if (h_counts) { (void)hipHostFree(h_counts); h_counts = nullptr; }
   }
 };
