@@ -25,7 +25,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-TILE = (64, 8, 8)              # map_reach.hip: the cells of a tile, x y z
+TILE = (64, 8, 8)              # map_relax.hpp: the cells of a tile, x y z
 
 
 @pytest.fixture(scope="module")
@@ -193,6 +193,31 @@ def test_blocked_is_where_the_device_distance_field_is_not_minus_1(env, fused, r
     got, _ = reach(pkg, ws, pool, case[1], origin, dims, case[4], seeds)
     assert np.array_equal(got == -2, dist2 != -1)
     same_field(dist2, field)
+
+
+# the smallest shapes with two tiles on x and a partial tile on each other axis
+NO_RING_CASES = [(9, 9, shape, "pt", clearance, 7) for shape in ((65, 9, 17), (130, 8, 8)) for clearance in (0, 1)]
+
+
+@pytest.mark.parametrize("case", NO_RING_CASES, ids=lambda c: "%dx%dx%d-r%d" % (*c[2], c[4]))
+def test_the_cost_field_without_rings_is_the_reach_field(env, fused, case):
+    """comfort_cells == clearance_cells: every weight is 1, and the two fields share map_relax's seed kernel, staging, write-back and
+    finish kernel, so they agree value for value and count the same seeds"""
+    pkg, torch = env
+    depth, d, shape, ox, clearance, count = case
+    pool, words, pts, ws = fused[depth]
+    origin, dims = case_region(words, d, shape, ox, clearance)
+    field = distance_field_separable(words, d, origin, dims, clearance)
+    seeds = seeds_for(field == -1, origin, dims, d, count, np.random.default_rng(100 + NO_RING_CASES.index(case)))
+    want = reach_field_words(words, d, origin, dims, clearance, seeds, field=field)
+    assert (want >= 1).sum() >= 50, int((want >= 1).sum())                   # on the restatement: the case is not empty
+    steps, reach_stats = reach(pkg, ws, pool, d, origin, dims, clearance, seeds)
+    cost_stats = {}
+    cost = pkg.cost_field(ws, pool, d, origin, dims, clearance, clearance, [], seeds, stats=cost_stats)
+    same_field(cost, steps)
+    same_field(steps, want)
+    assert cost_stats["seeds_used"] == reach_stats["seeds_used"] == int((want == 0).sum())
+    assert cost_stats["max_weight"] == 1
 
 
 def test_the_distance_field_is_unchanged_by_reach_calls_on_its_workspace(env, fused):
