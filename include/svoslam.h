@@ -687,6 +687,62 @@ int svoslam_pool_visibility_field(svoslam_workspace *ws, const svoslam_pool *poo
 /* diagnostics: the device pointer and size in bytes of the workspace's visibility slot (the bit rows; NULL / 0 before the first
  * call), as svoslam_workspace_field_buffers shows the distance field's.  Host only. */
 int svoslam_workspace_visibility_buffers(const svoslam_workspace *ws, void *d_ptrs[1], uint64_t bytes[1]);
+/* Viewpoints that cover a map region (no reference counterpart; specification here and in DESIGN.md section 24): out of n_cands
+ * places to stand, which few see the most of a set of target cells, and what is still unseen after them -- the question of an
+ * inspection or exploration planner, answered in one call: a compacted target list, a candidate-by-target bit matrix under
+ * svoslam_pool_visibility_field's sight rule, and a greedy set cover over it.  Exact, in integers, ties decided, all on the device.
+ *   d, N, the occupied set, the region and the order of a per-cell array (x fastest, [nz, ny, nx]) are exactly those of
+ *     svoslam_pool_distance_field.  R = range_cells, 0..SVOSLAM_MAX_RADIUS_CELLS.
+ *   Targets: a region cell is a target iff it passes target_mode and, where d_select is not NULL, its byte there is non-zero
+ *     (d_select: one uint8 per region cell in device memory, in region order).  SVOSLAM_COVER_SURFACE: the cell is occupied and at
+ *     least one of its six face neighbours lies in the root and is not occupied; a neighbour outside the region still counts, a
+ *     neighbour outside the root does not.  SVOSLAM_COVER_FREE: the cell is not occupied.  SVOSLAM_COVER_ALL: every cell.  Targets
+ *     are numbered in region order; T is their number.
+ *   Candidates: d_cands holds n_cands triples (x, y, z) of int32 absolute cells at depth d, in device memory, as
+ *     svoslam_pool_visibility_field's d_views.  A candidate COUNTS iff it lies in the root; it need not lie in the region, and
+ *     whether its own cell is occupied is ignored.  One that does not count sees nothing.  Duplicates are allowed; indices are
+ *     never renumbered.
+ *   Sight: svoslam_pool_visibility_field's rule, word for word: candidate c sees target q iff |q - v_c|^2 <= R^2 and no cell of
+ *     S(v_c, q) is occupied; edges and corners block, q == v is seen, an occupied q can be seen.
+ *   Scores: d_seen[c] = the number of targets c sees, 0 if it does not count.
+ *   Greedy cover: `covered` starts empty.  In round j = 0, 1, ...: gain(c) = the number of targets c sees that are not yet covered;
+ *     the round takes the candidate with the largest gain, among equal gains the LOWEST INDEX; if that gain is < min_gain, or
+ *     j == k_max, the cover ends; otherwise d_chosen[j] = c, d_gain[j] = gain, and the targets c sees become covered.  Entries past
+ *     the end are d_chosen = -1 and d_gain = 0.  min_gain >= 1; k_max is 0..SVOSLAM_MAX_COVER_VIEWS; k_max = 0 gives the scores and
+ *     the summary only, and d_chosen / d_gain may then be NULL.
+ *   d_round: one int32 per region cell: -1 not a target; -2 a target that no chosen candidate sees; otherwise the round j whose
+ *     candidate first covered it.  d_summary: four int32 (T, n_chosen, covered, coverable); coverable = the number of targets that
+ *     at least one candidate sees.  Only the values are specified, not how they are computed.
+ *   Conventions: those of svoslam_pool_visibility_field -- any pool; pending asynchronous fusions are drained first; a pool whose
+ *     deferred commit waits for its apply is read in its old state.  ONE THING DIFFERS: the call reads T back once (4 bytes) to
+ *     size the matrix, so it blocks until the target list is ranked, as svoslam_pool_reach_field blocks for its rounds; everything
+ *     after that readback, all k_max rounds included, is queued without another.  The intermediates live in four grow-only
+ *     workspace slots of their own (the occupancy bit rows of the region inflated by max(R, 1); flags / ranks and the target list;
+ *     the matrix, n_cands * ceil(T / 64) words of 64 bits; the covered words and one record per round), so a second call of the same
+ *     size allocates nothing, and no other call's slots are touched.
+ *   Errors: a zero entry of dims is SVOSLAM_OK: it writes the entries past the end (all k_max of them) and a zero summary and
+ *     nothing else.  T = 0 and n_cands = 0 are valid; d_cands may then be NULL.  SVOSLAM_ERR_INVALID_ARG: those of
+ *     svoslam_pool_visibility_field that concern the region, the range and the candidates; target_mode outside 0..2; k_max outside
+ *     0..SVOSLAM_MAX_COVER_VIEWS; min_gain < 1; NULL d_summary; NULL d_chosen or d_gain with k_max > 0 -- nothing is launched,
+ *     written or allocated.  SVOSLAM_ERR_POOL_LIMIT: more than 2^31 - 1 region cells or bit-row words, decided before anything is
+ *     allocated; a matrix of more than 2^29 words (4 GiB), decided right after the readback of T, before the matrix is allocated
+ *     and before any output is written -- what the call grew until then is released.  SVOSLAM_ERR_OOM: an allocation failed;
+ *     nothing the call grew stays behind.
+ *   Not part of it: a field-of-view cone or sensor model per candidate, weights per target, candidate poses rather than cells, an
+ *     optimal rather than greedy cover, the matrix as an output. */
+#define SVOSLAM_COVER_SURFACE 0
+#define SVOSLAM_COVER_FREE    1
+#define SVOSLAM_COVER_ALL     2
+#define SVOSLAM_MAX_COVER_VIEWS 1024
+int svoslam_pool_cover_views(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                             const int32_t dims[3], int32_t range_cells, int32_t target_mode, const uint8_t *d_select /* may be NULL */,
+                             const int32_t *d_cands, int32_t n_cands, int32_t k_max, int32_t min_gain,
+                             int32_t *d_seen /* n_cands, may be NULL */, int32_t *d_chosen /* k_max */, int32_t *d_gain /* k_max */,
+                             int32_t *d_round /* region cells, may be NULL */, int32_t *d_summary /* 4 */, void *stream);
+/* diagnostics: the device pointers and sizes in bytes of the workspace's four cover slots (the bit rows; flags / ranks and the
+ * target list; the matrix; the covered words and round records; NULL / 0 before the first call), as
+ * svoslam_workspace_visibility_buffers shows the visibility field's.  Host only. */
+int svoslam_workspace_cover_buffers(const svoslam_workspace *ws, void *d_ptrs[4], uint64_t bytes[4]);
 /* Scoring candidate poses against a distance field (no reference counterpart; specification here and in DESIGN.md section 20): for
  * each of n_poses sensor-to-world matrices, move each of n sensor points by it, look the point's cell up in the field of a region
  * and add the values up -- the inner loop of a likelihood-field or chamfer relocaliser ("where in this map was this depth frame
@@ -1125,7 +1181,7 @@ int svoslam_cone_trace_timing_read(float *h_ms_sum, int32_t *h_launches);
 #define SVOSLAM_STAGE_SURFACE_BFS 9    /* extract_surface_mesh: the occupied cells (incl. one readback per level) */
 #define SVOSLAM_STAGE_SURFACE_FACES 10 /* extract_surface_mesh: face masks + scan (incl. the count readback) | emission: two brackets per call, the host's allocations between them are outside */
 #define SVOSLAM_STAGE_SURFACE_WELD 11  /* extract_surface_mesh: corner sort + run heads + scan (incl. the count readback) | scatter: two brackets per call likewise */
-#define SVOSLAM_STAGE_QUERY 12         /* svoslam_pool_cast_rays / _query_points / _count_boxes / _nearest_occupied: the kernel, one bracket per call; svoslam_pool_distance_field: its four launches, one bracket per call; svoslam_pool_reach_field: the field's launches and every launch and readback of the relaxation, one bracket per call; svoslam_pool_label_components: the field's launches and its own, one bracket per call; svoslam_pool_nearest_field: its five launches, one bracket per call; svoslam_pool_visibility_field: its two launches, one bracket per call; svoslam_score_poses: its one to three launches, one bracket per call; svoslam_pool_cost_field: the field's launches and every launch and readback of the relaxation, one bracket per call; svoslam_field_trace_paths: its launch, one bracket per call */
+#define SVOSLAM_STAGE_QUERY 12         /* svoslam_pool_cast_rays / _query_points / _count_boxes / _nearest_occupied: the kernel, one bracket per call; svoslam_pool_distance_field: its four launches, one bracket per call; svoslam_pool_reach_field: the field's launches and every launch and readback of the relaxation, one bracket per call; svoslam_pool_label_components: the field's launches and its own, one bracket per call; svoslam_pool_nearest_field: its five launches, one bracket per call; svoslam_pool_visibility_field: its two launches, one bracket per call; svoslam_score_poses: its one to three launches, one bracket per call; svoslam_pool_cost_field: the field's launches and every launch and readback of the relaxation, one bracket per call; svoslam_field_trace_paths: its launch, one bracket per call; svoslam_pool_cover_views: its launches, the readback of T and all k_max rounds, one bracket per call */
 #define SVOSLAM_STAGE_COUNT 13
 int svoslam_stage_timing(uint32_t mask);
 int svoslam_stage_timing_read(int32_t stage, float *h_ms_sum, int32_t *h_pairs);

@@ -228,6 +228,9 @@ SIGNATURES = {
     "svoslam_pool_visibility_field": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _vp, _i32, _vp, _vp,
                                                 _vp]),
     "svoslam_workspace_visibility_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "svoslam_pool_cover_views": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _vp, _vp, _i32, _i32,
+                                           _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "svoslam_workspace_cover_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
     "svoslam_score_poses": (C.c_int, [_vp, _vp, _i32, _fp, _f32, C.POINTER(_i32), C.POINTER(_i32), _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp,
                                       _vp, _vp, _vp, _vp]),
     "svoslam_workspace_score_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
@@ -449,6 +452,13 @@ class Workspace:
         ptrs, sizes = (_vp * 1)(), (C.c_uint64 * 1)()
         check(lib().svoslam_workspace_visibility_buffers(self._h, ptrs, sizes))
         return [(int(ptrs[0] or 0), int(sizes[0]))]
+
+    def cover_buffers(self):
+        """svoslam_workspace_cover_buffers: [(device pointer, bytes)] of the view cover's four slots -- the bit rows, the flags / ranks
+        and the target list, the matrix, the covered words and round records (diagnostics)"""
+        ptrs, sizes = (_vp * 4)(), (C.c_uint64 * 4)()
+        check(lib().svoslam_workspace_cover_buffers(self._h, ptrs, sizes))
+        return [(int(ptrs[k] or 0), int(sizes[k])) for k in range(4)]
 
     def score_buffers(self):
         """svoslam_workspace_score_buffers: [(device pointer, bytes)] of the pose scoring's one slot (diagnostics)"""
@@ -1409,6 +1419,62 @@ def visibility_field(ws, pool, max_depth, origin, dims, range_cells, views, want
     if as_tensor:
         return bufs
     return {name: b.cpu().numpy().view(fields[name][1]) for name, b in bufs.items()}
+
+
+COVER_SURFACE, COVER_FREE, COVER_ALL = 0, 1, 2                          # include/svoslam.h SVOSLAM_COVER_*
+COVER_TARGETS = {"surface": COVER_SURFACE, "free": COVER_FREE, "all": COVER_ALL}
+MAX_COVER_VIEWS = 1024                                                  # include/svoslam.h SVOSLAM_MAX_COVER_VIEWS
+COVER_OUTPUTS = ("seen", "chosen", "gain", "round", "summary")
+
+
+def cover_views(ws, pool, max_depth, origin, dims, range_cells, candidates, k_max, min_gain=1, targets="surface", select=None,
+                want=COVER_OUTPUTS, as_tensor=False):
+    """svoslam_pool_cover_views: which of the `candidates` ([n, 3] absolute cells at max_depth: an array, or an int32 cuda tensor)
+    see the most of the target cells of the region origin[3] .. origin + dims[3], by svoslam_pool_visibility_field's sight rule
+    within range_cells, and a greedy set cover of at most k_max rounds over them: each round takes the candidate that sees the most
+    targets not yet covered, the lowest index among equals, until that gain is below min_gain.  `targets`: "surface" (occupied
+    cells with a free face neighbour in the root), "free" or "all", or a COVER_* value; `select`: None, or one byte per region cell
+    ([nz, ny, nx]: an array, or a uint8 / bool cuda tensor) -- only cells with a non-zero byte are targets.  `want`: the subset of
+    "seen" (int32 [n]: the targets each candidate sees), "chosen" and "gain" (int32 [k_max]: -1 / 0 past the end), "round" (int32
+    [nz, ny, nx]: -1 not a target, -2 a target no chosen candidate sees, else the round that first covered it) and "summary"
+    (int32 [4]: targets, chosen, covered, coverable) to return.  -> a dict: numpy, or with as_tensor cuda tensors.  The call itself
+    reads the number of targets back once."""
+    import torch
+    o, n = [int(v) for v in origin], [int(v) for v in dims]
+    if len(o) != 3 or len(n) != 3:
+        raise ValueError("origin and dims are three cells each (x, y, z)")
+    names = tuple(want)
+    for name in names:
+        if name not in COVER_OUTPUTS:
+            raise KeyError("no output %r (have: %s)" % (name, ", ".join(COVER_OUTPUTS)))
+    mode = COVER_TARGETS[targets] if isinstance(targets, str) else int(targets)
+    t_cands = _device_array(candidates, torch.int32, np.int32, 3, "candidates")
+    count, k = int(t_cands.shape[0]), int(k_max)
+    shape = [max(v, 0) for v in reversed(n)]
+    t_select = None
+    if select is not None:
+        if isinstance(select, torch.Tensor):
+            if not select.is_cuda or select.dtype not in (torch.uint8, torch.bool):
+                raise ValueError("a select tensor is uint8 or bool on the device")
+            t_select = select.contiguous().view(torch.uint8)
+        else:
+            t_select = torch.from_numpy(np.ascontiguousarray(np.asarray(select) != 0).view(np.uint8)).cuda()
+        if t_select.numel() != shape[0] * shape[1] * shape[2]:
+            raise ValueError("select has one byte per region cell")
+    bufs = {"summary": torch.empty(4, dtype=torch.int32, device="cuda")}
+    if "seen" in names:
+        bufs["seen"] = torch.zeros(count, dtype=torch.int32, device="cuda")      # a region without cells leaves it unwritten
+    if k > 0 or "chosen" in names or "gain" in names:
+        bufs["chosen"] = torch.empty(max(k, 0), dtype=torch.int32, device="cuda")
+        bufs["gain"] = torch.empty(max(k, 0), dtype=torch.int32, device="cuda")
+    if "round" in names:
+        bufs["round"] = torch.empty(shape, dtype=torch.int32, device="cuda")
+    check(lib().svoslam_pool_cover_views(ws._h, C.byref(pool._p), int(max_depth), (_i32 * 3)(*o), (_i32 * 3)(*n), int(range_cells), mode,
+                                         _ptr(t_select), _ptr(t_cands) if count else None, count, k, int(min_gain),
+                                         *[_ptr(bufs.get(name)) if name not in ("chosen", "gain") or k > 0 else None
+                                           for name in COVER_OUTPUTS], _stream()))
+    out = {name: bufs[name] for name in names}
+    return out if as_tensor else {name: b.cpu().numpy() for name, b in out.items()}
 
 
 MAX_MISS_COST = 1 << 30                                                 # include/svoslam.h SVOSLAM_MAX_MISS_COST

@@ -9,6 +9,7 @@
 #include "icp.hpp"
 #include "image_kernels.hpp"
 #include "map_components.hpp"
+#include "map_coverage.hpp"
 #include "map_field.hpp"
 #include "map_ground.hpp"
 #include "map_nearest.hpp"
@@ -476,6 +477,22 @@ int svoslam_workspace_visibility_buffers(const svoslam_workspace *ws, void *d_pt
   if (!ws || !d_ptrs || !bytes) return SVOSLAM_ERR_INVALID_ARG;
   d_ptrs[0] = ws->vis_bits.ptr;
   bytes[0] = ws->vis_bits.bytes;
+  return SVOSLAM_OK;
+}
+
+int svoslam_pool_cover_views(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                             const int32_t dims[3], int32_t range_cells, int32_t target_mode, const uint8_t *d_select,
+                             const int32_t *d_cands, int32_t n_cands, int32_t k_max, int32_t min_gain, int32_t *d_seen, int32_t *d_chosen,
+                             int32_t *d_gain, int32_t *d_round, int32_t *d_summary, void *stream) {
+  NEED_DEVICE();
+  return pool_cover_views(ws, pool, max_depth, origin_cell, dims, range_cells, target_mode, d_select, d_cands, n_cands, k_max, min_gain,
+                          d_seen, d_chosen, d_gain, d_round, d_summary, S(stream));
+}
+
+int svoslam_workspace_cover_buffers(const svoslam_workspace *ws, void *d_ptrs[4], uint64_t bytes[4]) {
+  if (!ws || !d_ptrs || !bytes) return SVOSLAM_ERR_INVALID_ARG;
+  const svoslam::DeviceBuffer *slots[4] = {&ws->cov_bits, &ws->cov_targets, &ws->cov_matrix, &ws->cov_state};
+  for (int k = 0; k < 4; k++) { d_ptrs[k] = slots[k]->ptr; bytes[k] = slots[k]->bytes; }
   return SVOSLAM_OK;
 }
 

@@ -2,6 +2,8 @@
 // inflated by a radius and clipped to the root, its raster into bit rows, the exact truncated distance transform of those rows, the
 // packing of a field's -1 into bit rows of the region itself, and the rollback of the workspace slots a failed call grew
 #pragma once
+#include <initializer_list>
+
 #include "workspace.hpp"
 
 namespace svoslam {
@@ -54,15 +56,21 @@ bool planar_within_limits(const RegionPlan &p, int pass_axis);
 // is then overwritten with *none
 int region_pack(const RegionPlan &own, int32_t *values, bool invert, const int *none, unsigned long long *bits, hipStream_t stream);
 
-// pool_distance_field first, then the caller's own two or three slots: what this call grew of them does not stay behind a failure
+// what a call grew of the listed slots (at most 6; a NULL entry is skipped) does not stay behind a failure
 struct SlotRollback {
   DeviceBuffer *slots[6];
   size_t had[6];
-  int n;
-  SlotRollback(svoslam_workspace *ws, DeviceBuffer *own_a, DeviceBuffer *own_b, DeviceBuffer *own_c = nullptr)
-      : slots{&ws->field_bits, &ws->field_a, &ws->field_b, own_a, own_b, own_c}, n(own_c ? 6 : 5) {
-    for (int k = 0; k < n; k++) had[k] = slots[k]->bytes;
+  int n = 0;
+  SlotRollback(std::initializer_list<DeviceBuffer *> list) {
+    for (DeviceBuffer *slot : list)
+      if (slot && n < 6) {
+        slots[n] = slot;
+        had[n++] = slot->bytes;
+      }
   }
+  // pool_distance_field's slots first, then the caller's own two or three
+  SlotRollback(svoslam_workspace *ws, DeviceBuffer *own_a, DeviceBuffer *own_b, DeviceBuffer *own_c = nullptr)
+      : SlotRollback({&ws->field_bits, &ws->field_a, &ws->field_b, own_a, own_b, own_c}) {}
   int undo(int rc, hipStream_t stream) {  // the field's launches have finished before their slots go
     (void)hipStreamSynchronize(stream);
     for (int k = 0; k < n; k++)
