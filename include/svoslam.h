@@ -743,6 +743,84 @@ int svoslam_pool_cover_views(svoslam_workspace *ws, const svoslam_pool *pool, in
  * target list; the matrix; the covered words and round records; NULL / 0 before the first call), as
  * svoslam_workspace_visibility_buffers shows the visibility field's.  Host only. */
 int svoslam_workspace_cover_buffers(const svoslam_workspace *ws, void *d_ptrs[4], uint64_t bytes[4]);
+/* The observed space of a map region (no reference counterpart; specification here and in DESIGN.md section 25).  Every region
+ * field above treats "not occupied" as "free"; these two calls tell a cell a sensor looked through from a cell nothing ever looked
+ * at, beside the map: the pool, the fusion and every other call are untouched.  Together with svoslam_pool_cover_views they close
+ * the loop of an exploring robot: observe, find the frontier of the known, choose the next views of it, plan to them.
+ *
+ * svoslam_field_observe_rays: what a set of sensor rays has seen
+ *   Like svoslam_score_poses the call sees no pool.  d = max_depth, N = 2^d; the planes P_a(k) and the count c_a(p) are
+ *     svoslam_pool_cast_rays' (center, edge_length as there).  The region has to lie inside the root, by
+ *     svoslam_pool_distance_field's test.
+ *   d_obs: one uint8 per region cell in device memory, x fastest ([nz, ny, nx]).  d_points: n_frames blocks of n triples of binary32
+ *     in the sensor frame, frame f at d_points + 3 n f: what svoslam_generate_vertex_map writes.  d_poses: n_frames x 16 binary32,
+ *     each a sensor-to-world matrix in the layout of every trans[16] of this header.
+ *   One ray (frame f with pose M, point p), classified in this order:
+ *     1. VOID if a component of p is not finite;
+ *     2. otherwise o = (m[12], m[13], m[14]) and w = M * (p, 1) in binary32 in the operation order of
+ *        svoslam_transform_vertex_map, no fused multiply-add: step 1 of svoslam_score_poses;
+ *     3. OUTSIDE if a component of o or of w is not finite or fails the root test P_a(0) <= . <= P_a(N) on any axis;
+ *     4. otherwise s_a = c_a(o_a) and e_a = c_a(w_a), the non-strict count svoslam_pool_nearest_occupied gives a point;
+ *     5. with D = e - s: FAR if range_cells > 0 and |D|^2 > range_cells^2 (compared in 64 bits); range_cells = 0 is no limit,
+ *        the valid range is 0..2^SVOSLAM_MAX_DEPTH.  A far ray is skipped whole, not truncated;
+ *     6. otherwise MARKED: e gets SVOSLAM_OBS_END; if s != e, s and every cell of S(s, e) get SVOSLAM_OBS_THROUGH, S being the
+ *        supercover without its ends of svoslam_pool_visibility_field (edges and corners touched count).  Only cells of the region
+ *        are stored; a MARKED ray whose cells all lie outside the region marks nothing and still counts as MARKED.
+ *   The result is a set: it does not depend on the order of rays, lanes or frames.  accumulate == 0: d_obs[q] = the marks of this
+ *     call, its other bits 0.  accumulate != 0: d_obs[q] |= the marks; bits 2..7 are left as found.
+ *   d_summary: six int64 in device memory (void, outside, far, marked, cells_through, cells_end); the last two count the region
+ *     cells whose bit is set in d_obs AFTER the call.  May be NULL.  Nothing is read back; everything is queued on `stream`.
+ *   Workspace: the two bit planes over the region's rows live in one grow-only slot of their own; the six counts are added
+ *     straight into d_summary.  A second call of the same size allocates nothing, no other call's slot is touched.
+ *   Errors: a zero entry of dims is SVOSLAM_OK: it writes the summary's four ray counts (every non-void ray in the root and in
+ *     range is MARKED) and zero cell counts.  n == 0 or n_frames == 0 is valid: d_obs is cleared, or left unchanged under
+ *     accumulate.  SVOSLAM_ERR_INVALID_ARG: NULL ws, center, origin_cell or dims; max_depth outside 1..SVOSLAM_MAX_DEPTH;
+ *     !(edge_length > 0); a negative entry of dims; a region not inside the root; n < 0; n_frames < 0; range_cells outside
+ *     0..2^SVOSLAM_MAX_DEPTH; NULL d_obs with a non-empty region; NULL d_points or d_poses with n * n_frames > 0.
+ *     SVOSLAM_ERR_POOL_LIMIT: more than 2^31 - 1 region cells, or n * n_frames > 2^31 - 1.  SVOSLAM_ERR_OOM: the allocation
+ *     failed.  On an error nothing is launched, written or allocated, and what the call grew is released.
+ *   Not part of it: changing the pool; truncating a long ray at the range; rays with an end outside the root; ray counts per cell;
+ *     a noise model.
+ *
+ * svoslam_pool_frontier_field: the observation held against the map
+ *   d, N, the occupied set, the region and the order are exactly those of svoslam_pool_distance_field.  d_obs as above; T is a
+ *     cell's THROUGH bit, E its END bit, the other bits are ignored.  The state of a cell:
+ *       SVOSLAM_STATE_UNKNOWN   not occupied, neither bit
+ *       SVOSLAM_STATE_FREE      not occupied, T, not E
+ *       SVOSLAM_STATE_FRONTIER  FREE, and at least one of its six face neighbours lies in the REGION and is UNKNOWN
+ *       SVOSLAM_STATE_OCCUPIED  occupied, and not (T without E)
+ *       SVOSLAM_STATE_VACATED   occupied, T, not E: rays passed through it and none ended in it -- evidence, not proof: a grazing
+ *                               ray touches a wall's cells too
+ *       SVOSLAM_STATE_UNMAPPED  not occupied, E
+ *     A neighbour outside the region never makes a frontier: its state is not known to the call.
+ *   Outputs, each may be NULL, not all three: d_state, one uint8 per region cell; d_frontier, 1 iff the state is FRONTIER, else 0:
+ *     directly svoslam_pool_cover_views' d_select; d_summary, six int32: the number of cells per state.
+ *   Conventions: those of svoslam_pool_visibility_field -- any pool; pending asynchronous fusions are drained first; a pool whose
+ *     deferred commit waits for its apply is read in its old state; nothing is read back.  The one intermediate, the occupancy of
+ *     the region itself as bit rows, lives in one grow-only workspace slot of its own.
+ *   Errors: those of svoslam_pool_visibility_field for the region (a zero entry of dims is SVOSLAM_OK and writes a zero summary);
+ *     SVOSLAM_ERR_INVALID_ARG also for NULL d_obs with a non-empty region and for all three outputs NULL.
+ *   Not part of it: frontier clustering; a frontier across the region's border; thresholds on counts. */
+#define SVOSLAM_OBS_THROUGH 1
+#define SVOSLAM_OBS_END     2
+#define SVOSLAM_STATE_UNKNOWN  0
+#define SVOSLAM_STATE_FREE     1
+#define SVOSLAM_STATE_FRONTIER 2
+#define SVOSLAM_STATE_OCCUPIED 3
+#define SVOSLAM_STATE_VACATED  4
+#define SVOSLAM_STATE_UNMAPPED 5
+int svoslam_field_observe_rays(svoslam_workspace *ws, uint8_t *d_obs, int32_t max_depth, const float center[3], float edge_length,
+                               const int32_t origin_cell[3], const int32_t dims[3], const float *d_points, int32_t n,
+                               const float *d_poses, int32_t n_frames, int32_t range_cells, int32_t accumulate,
+                               int64_t *d_summary /* 6, may be NULL */, void *stream);
+int svoslam_pool_frontier_field(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                                const int32_t dims[3], const uint8_t *d_obs, uint8_t *d_state /* may be NULL */,
+                                uint8_t *d_frontier /* may be NULL */, int32_t *d_summary /* 6, may be NULL */, void *stream);
+/* diagnostics: the device pointer and size in bytes of the workspace's observation slot (the two bit planes) and of its frontier
+ * slot (the bit rows; NULL / 0 before the first call), as svoslam_workspace_visibility_buffers shows the visibility field's.  Host
+ * only. */
+int svoslam_workspace_observe_buffers(const svoslam_workspace *ws, void *d_ptrs[1], uint64_t bytes[1]);
+int svoslam_workspace_frontier_buffers(const svoslam_workspace *ws, void *d_ptrs[1], uint64_t bytes[1]);
 /* Scoring candidate poses against a distance field (no reference counterpart; specification here and in DESIGN.md section 20): for
  * each of n_poses sensor-to-world matrices, move each of n sensor points by it, look the point's cell up in the field of a region
  * and add the values up -- the inner loop of a likelihood-field or chamfer relocaliser ("where in this map was this depth frame
@@ -1181,7 +1259,7 @@ int svoslam_cone_trace_timing_read(float *h_ms_sum, int32_t *h_launches);
 #define SVOSLAM_STAGE_SURFACE_BFS 9    /* extract_surface_mesh: the occupied cells (incl. one readback per level) */
 #define SVOSLAM_STAGE_SURFACE_FACES 10 /* extract_surface_mesh: face masks + scan (incl. the count readback) | emission: two brackets per call, the host's allocations between them are outside */
 #define SVOSLAM_STAGE_SURFACE_WELD 11  /* extract_surface_mesh: corner sort + run heads + scan (incl. the count readback) | scatter: two brackets per call likewise */
-#define SVOSLAM_STAGE_QUERY 12         /* svoslam_pool_cast_rays / _query_points / _count_boxes / _nearest_occupied: the kernel, one bracket per call; svoslam_pool_distance_field: its four launches, one bracket per call; svoslam_pool_reach_field: the field's launches and every launch and readback of the relaxation, one bracket per call; svoslam_pool_label_components: the field's launches and its own, one bracket per call; svoslam_pool_nearest_field: its five launches, one bracket per call; svoslam_pool_visibility_field: its two launches, one bracket per call; svoslam_score_poses: its one to three launches, one bracket per call; svoslam_pool_cost_field: the field's launches and every launch and readback of the relaxation, one bracket per call; svoslam_field_trace_paths: its launch, one bracket per call; svoslam_pool_cover_views: its launches, the readback of T and all k_max rounds, one bracket per call */
+#define SVOSLAM_STAGE_QUERY 12         /* svoslam_pool_cast_rays / _query_points / _count_boxes / _nearest_occupied: the kernel, one bracket per call; svoslam_pool_distance_field: its four launches, one bracket per call; svoslam_pool_reach_field: the field's launches and every launch and readback of the relaxation, one bracket per call; svoslam_pool_label_components: the field's launches and its own, one bracket per call; svoslam_pool_nearest_field: its five launches, one bracket per call; svoslam_pool_visibility_field: its two launches, one bracket per call; svoslam_score_poses: its one to three launches, one bracket per call; svoslam_pool_cost_field: the field's launches and every launch and readback of the relaxation, one bracket per call; svoslam_field_trace_paths: its launch, one bracket per call; svoslam_pool_cover_views: its launches, the readback of T and all k_max rounds, one bracket per call; svoslam_field_observe_rays: its two clears and two launches, one bracket per call; svoslam_pool_frontier_field: its clear and two launches, one bracket per call */
 #define SVOSLAM_STAGE_COUNT 13
 int svoslam_stage_timing(uint32_t mask);
 int svoslam_stage_timing_read(int32_t stage, float *h_ms_sum, int32_t *h_pairs);

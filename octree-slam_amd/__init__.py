@@ -231,6 +231,11 @@ SIGNATURES = {
     "svoslam_pool_cover_views": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _vp, _vp, _i32, _i32,
                                            _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "svoslam_workspace_cover_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "svoslam_field_observe_rays": (C.c_int, [_vp, _vp, _i32, _fp, _f32, C.POINTER(_i32), C.POINTER(_i32), _vp, _i32, _vp, _i32, _i32, _i32, _vp,
+                                             _vp]),
+    "svoslam_workspace_observe_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "svoslam_pool_frontier_field": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, C.POINTER(_i32), C.POINTER(_i32), _vp, _vp, _vp, _vp, _vp]),
+    "svoslam_workspace_frontier_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
     "svoslam_score_poses": (C.c_int, [_vp, _vp, _i32, _fp, _f32, C.POINTER(_i32), C.POINTER(_i32), _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp,
                                       _vp, _vp, _vp, _vp]),
     "svoslam_workspace_score_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
@@ -459,6 +464,18 @@ class Workspace:
         ptrs, sizes = (_vp * 4)(), (C.c_uint64 * 4)()
         check(lib().svoslam_workspace_cover_buffers(self._h, ptrs, sizes))
         return [(int(ptrs[k] or 0), int(sizes[k])) for k in range(4)]
+
+    def observe_buffers(self):
+        """svoslam_workspace_observe_buffers: [(device pointer, bytes)] of the ray observation's one slot, the two bit planes (diagnostics)"""
+        ptrs, sizes = (_vp * 1)(), (C.c_uint64 * 1)()
+        check(lib().svoslam_workspace_observe_buffers(self._h, ptrs, sizes))
+        return [(int(ptrs[0] or 0), int(sizes[0]))]
+
+    def frontier_buffers(self):
+        """svoslam_workspace_frontier_buffers: [(device pointer, bytes)] of the frontier field's one slot, the bit rows (diagnostics)"""
+        ptrs, sizes = (_vp * 1)(), (C.c_uint64 * 1)()
+        check(lib().svoslam_workspace_frontier_buffers(self._h, ptrs, sizes))
+        return [(int(ptrs[0] or 0), int(sizes[0]))]
 
     def score_buffers(self):
         """svoslam_workspace_score_buffers: [(device pointer, bytes)] of the pose scoring's one slot (diagnostics)"""
@@ -1475,6 +1492,99 @@ def cover_views(ws, pool, max_depth, origin, dims, range_cells, candidates, k_ma
                                            for name in COVER_OUTPUTS], _stream()))
     out = {name: bufs[name] for name in names}
     return out if as_tensor else {name: b.cpu().numpy() for name, b in out.items()}
+
+
+OBS_THROUGH, OBS_END = 1, 2                                             # include/svoslam.h SVOSLAM_OBS_*
+STATE_UNKNOWN, STATE_FREE, STATE_FRONTIER, STATE_OCCUPIED, STATE_VACATED, STATE_UNMAPPED = range(6)   # include/svoslam.h SVOSLAM_STATE_*
+STATE_NAMES = ("unknown", "free", "frontier", "occupied", "vacated", "unmapped")
+FRONTIER_OUTPUTS = ("state", "frontier", "summary")
+
+
+def observe_rays(ws, obs, max_depth, center, edge_length, origin, dims, points, poses, range_cells=0, accumulate=False, as_tensor=False):
+    """svoslam_field_observe_rays: what the sensor rays of `poses` ([F, 16] float32, sensor to world, the layout of every trans[16])
+    and `points` ([F, n, 3] float32 in the sensor frame, frame f's points with pose f; e.g. vertex maps) have seen of the region
+    origin[3] .. origin + dims[3] (cells at max_depth, x y z): per cell bit OBS_THROUGH, a ray passed through it, and bit OBS_END, a
+    ray ended in it.  A point that is not finite is void; a ray with an end outside the root is outside; with range_cells > 0 a ray
+    longer than that many cells is far, and skipped whole.  `obs`: None for a new array, or the uint8 [nz, ny, nx] to write (an
+    array, or a uint8 cuda tensor, which is written in place); with `accumulate` the marks are ORed into it and its bits 2..7 are
+    kept, else it is overwritten.  points and poses may be cuda tensors (used in place) or arrays (uploaded).  -> (obs, summary):
+    summary is int64 [6] = rays void, outside, far, marked, then the region cells with THROUGH and with END after the call.  numpy,
+    or with as_tensor cuda tensors, in which case nothing is synchronised."""
+    import torch
+    o, n3 = [int(v) for v in origin], [int(v) for v in dims]
+    if len(o) != 3 or len(n3) != 3:
+        raise ValueError("origin and dims are three cells each (x, y, z)")
+    shape = [max(v, 0) for v in reversed(n3)]
+    t_poses = _device_array(poses, torch.float32, np.float32, 16, "poses")
+    t_points = _device_array(points, torch.float32, np.float32, 3, "points")
+    frames = int(t_poses.shape[0])
+    rows = int(t_points.shape[0])
+    if (frames == 0 and rows != 0) or (frames > 0 and rows % frames != 0):
+        raise ValueError("%d points are not %d frames of equally many" % (rows, frames))
+    n = rows // frames if frames else 0
+    if obs is None:
+        if accumulate:
+            raise ValueError("accumulate needs the obs to add to")
+        t_obs = torch.empty(shape, dtype=torch.uint8, device="cuda")
+    elif isinstance(obs, torch.Tensor):
+        if not obs.is_cuda or obs.dtype != torch.uint8 or not obs.is_contiguous():
+            raise ValueError("an obs tensor is contiguous uint8 on the device")
+        t_obs = obs
+    else:
+        t_obs = torch.from_numpy(np.ascontiguousarray(np.asarray(obs, np.uint8))).cuda()
+    if t_obs.numel() != shape[0] * shape[1] * shape[2]:
+        raise ValueError("obs has one byte per region cell")
+    t_obs = t_obs.view(shape)
+    summary = torch.empty(6, dtype=torch.int64, device="cuda")
+    check(lib().svoslam_field_observe_rays(ws._h, _ptr(t_obs) if t_obs.numel() else None, int(max_depth), _fa(center, 3), float(edge_length),
+                                           (_i32 * 3)(*o), (_i32 * 3)(*n3), _ptr(t_points) if n * frames else None, n,
+                                           _ptr(t_poses) if n * frames else None, frames, int(range_cells), 1 if accumulate else 0,
+                                           _ptr(summary), _stream()))
+    if as_tensor:
+        return t_obs, summary
+    return t_obs.cpu().numpy(), summary.cpu().numpy()
+
+
+def frontier_field(ws, pool, max_depth, origin, dims, obs, want=FRONTIER_OUTPUTS, as_tensor=False):
+    """svoslam_pool_frontier_field: observe_rays' `obs` (uint8 [nz, ny, nx]: an array, or a uint8 cuda tensor) held against the map
+    over the region origin[3] .. origin + dims[3]: "state" (uint8 [nz, ny, nx]: STATE_UNKNOWN, STATE_FREE, STATE_FRONTIER -- free
+    with a face neighbour in the region that is unknown --, STATE_OCCUPIED, STATE_VACATED -- occupied, rays passed through it and
+    none ended in it --, STATE_UNMAPPED -- a ray ended where the map has nothing), "frontier" (uint8 [nz, ny, nx]: 1 where the state
+    is STATE_FRONTIER; cover_views' select) and "summary" (int32 [6]: the cells per state).  `want`: the subset to compute; the
+    others are passed as NULL.  -> a dict: numpy, or with as_tensor cuda tensors, in which case nothing is synchronised."""
+    import torch
+    o, n3 = [int(v) for v in origin], [int(v) for v in dims]
+    if len(o) != 3 or len(n3) != 3:
+        raise ValueError("origin and dims are three cells each (x, y, z)")
+    names = tuple(want)
+    for name in names:
+        if name not in FRONTIER_OUTPUTS:
+            raise KeyError("no output %r (have: %s)" % (name, ", ".join(FRONTIER_OUTPUTS)))
+    shape = [max(v, 0) for v in reversed(n3)]
+    if isinstance(obs, torch.Tensor):
+        if not obs.is_cuda or obs.dtype != torch.uint8:
+            raise ValueError("an obs tensor is uint8 on the device")
+        t_obs = obs.contiguous()
+    else:
+        t_obs = torch.from_numpy(np.ascontiguousarray(np.asarray(obs, np.uint8))).cuda()
+    if t_obs.numel() != shape[0] * shape[1] * shape[2]:
+        raise ValueError("obs has one byte per region cell")
+    bufs = {name: torch.empty(6, dtype=torch.int32, device="cuda") if name == "summary" else torch.empty(shape, dtype=torch.uint8, device="cuda")
+            for name in names}
+    check(lib().svoslam_pool_frontier_field(ws._h, C.byref(pool._p), int(max_depth), (_i32 * 3)(*o), (_i32 * 3)(*n3),
+                                            _ptr(t_obs) if t_obs.numel() else None, *[_ptr(bufs.get(name)) for name in FRONTIER_OUTPUTS],
+                                            _stream()))
+    return bufs if as_tensor else {name: b.cpu().numpy() for name, b in bufs.items()}
+
+
+def explore_views(ws, pool, max_depth, origin, dims, obs, candidates, range_cells, k_max, min_gain=1):
+    """Where to look next: frontier_field of `obs`, then cover_views of the region's free cells selected by the frontier bytes --
+    which few of the `candidates` ([n, 3] absolute cells) see the most of the boundary between the observed free space and the
+    unknown within range_cells.  The frontier stays on the device between the two calls.  -> (frontier_field's dict, cover_views'
+    dict), numpy."""
+    field = frontier_field(ws, pool, max_depth, origin, dims, obs, as_tensor=True)
+    cover = cover_views(ws, pool, max_depth, origin, dims, range_cells, candidates, k_max, min_gain, "free", field["frontier"])
+    return {name: b.cpu().numpy() for name, b in field.items()}, cover
 
 
 MAX_MISS_COST = 1 << 30                                                 # include/svoslam.h SVOSLAM_MAX_MISS_COST

@@ -13,6 +13,7 @@
 #include "map_field.hpp"
 #include "map_ground.hpp"
 #include "map_nearest.hpp"
+#include "map_observe.hpp"
 #include "map_paths.hpp"
 #include "map_plan.hpp"
 #include "map_query.hpp"
@@ -493,6 +494,36 @@ int svoslam_workspace_cover_buffers(const svoslam_workspace *ws, void *d_ptrs[4]
   if (!ws || !d_ptrs || !bytes) return SVOSLAM_ERR_INVALID_ARG;
   const svoslam::DeviceBuffer *slots[4] = {&ws->cov_bits, &ws->cov_targets, &ws->cov_matrix, &ws->cov_state};
   for (int k = 0; k < 4; k++) { d_ptrs[k] = slots[k]->ptr; bytes[k] = slots[k]->bytes; }
+  return SVOSLAM_OK;
+}
+
+int svoslam_field_observe_rays(svoslam_workspace *ws, uint8_t *d_obs, int32_t max_depth, const float center[3], float edge_length,
+                               const int32_t origin_cell[3], const int32_t dims[3], const float *d_points, int32_t n,
+                               const float *d_poses, int32_t n_frames, int32_t range_cells, int32_t accumulate, int64_t *d_summary,
+                               void *stream) {
+  NEED_DEVICE();
+  return field_observe_rays(ws, d_obs, max_depth, center, edge_length, origin_cell, dims, d_points, n, d_poses, n_frames, range_cells,
+                            accumulate, d_summary, S(stream));
+}
+
+int svoslam_workspace_observe_buffers(const svoslam_workspace *ws, void *d_ptrs[1], uint64_t bytes[1]) {
+  if (!ws || !d_ptrs || !bytes) return SVOSLAM_ERR_INVALID_ARG;
+  d_ptrs[0] = ws->obs_bits.ptr;
+  bytes[0] = ws->obs_bits.bytes;
+  return SVOSLAM_OK;
+}
+
+int svoslam_pool_frontier_field(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                                const int32_t dims[3], const uint8_t *d_obs, uint8_t *d_state, uint8_t *d_frontier, int32_t *d_summary,
+                                void *stream) {
+  NEED_DEVICE();
+  return pool_frontier_field(ws, pool, max_depth, origin_cell, dims, d_obs, d_state, d_frontier, d_summary, S(stream));
+}
+
+int svoslam_workspace_frontier_buffers(const svoslam_workspace *ws, void *d_ptrs[1], uint64_t bytes[1]) {
+  if (!ws || !d_ptrs || !bytes) return SVOSLAM_ERR_INVALID_ARG;
+  d_ptrs[0] = ws->front_bits.ptr;
+  bytes[0] = ws->front_bits.bytes;
   return SVOSLAM_OK;
 }
 

@@ -23,7 +23,7 @@ enum Stage {
   kStageSurfaceBfs = SVOSLAM_STAGE_SURFACE_BFS,      // svo_surface.hip: the occupied cells (bfs_occupied_keys, incl. one readback per level)
   kStageSurfaceFaces = SVOSLAM_STAGE_SURFACE_FACES,  // svo_surface.hip: face masks + scan (incl. the count readback) | emission: two brackets per call
   kStageSurfaceWeld = SVOSLAM_STAGE_SURFACE_WELD,    // svo_surface.hip: corner sort + run heads + scan (incl. the count readback) | scatter: two brackets per call
-  kStageQuery = SVOSLAM_STAGE_QUERY,               // map_query.hip, map_volume.hip, map_field.hip (with map_region.hip's launches), map_reach.hip, map_components.hip, map_nearest.hip, map_visibility.hip, map_coverage.hip, map_score.hip, map_plan.hip, map_paths.hip, map_ground.hip: one bracket per call around the query's kernel(s); map_relax.hip opens none, its callers' brackets hold its launches
+  kStageQuery = SVOSLAM_STAGE_QUERY,               // map_query.hip, map_volume.hip, map_field.hip (with map_region.hip's launches), map_reach.hip, map_components.hip, map_nearest.hip, map_visibility.hip, map_coverage.hip, map_observe.hip, map_score.hip, map_plan.hip, map_paths.hip, map_ground.hip: one bracket per call around the query's kernel(s); map_relax.hip opens none, its callers' brackets hold its launches
   kStageCount = SVOSLAM_STAGE_COUNT
 };
 

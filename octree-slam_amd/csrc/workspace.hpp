@@ -63,6 +63,8 @@ struct svoslam_workspace {
   svoslam::DeviceBuffer near_bits, near_dist, near_arg;   // nearest-cell field: target bit rows of the inflated region; the values after the x, y and z pass; the three passes' 16-bit indices
   svoslam::DeviceBuffer vis_bits;                         // visibility field: occupancy bit rows of the region inflated by the range
   svoslam::DeviceBuffer cov_bits, cov_targets, cov_matrix, cov_state;  // view cover: occupancy bit rows of the region inflated by max(range, 1); flags / ranks, the target list and T; the candidate-by-target bit matrix; the covered words + one record per round
+  svoslam::DeviceBuffer obs_bits;                         // ray observation: the THROUGH and the END bit plane over the region's rows
+  svoslam::DeviceBuffer front_bits;                       // frontier field: occupancy bit rows of the region itself
   svoslam::DeviceBuffer score_rec;                        // pose scoring: a 32-byte record (cost, near, far, outside) per pose, when the call accumulates across workgroups or its caller wants only the best
   svoslam::DeviceBuffer misc;                            // bbox partials etc.
   svoslam::DeviceBuffer scan_tmp;                         // chunk sums of exclusive_scan_u32
@@ -91,7 +93,7 @@ struct svoslam_workspace {
     leaf_t.release(); leaf_f.release(); rec_key.release(); rec_front.release(); path_nodes.release(); strad.release();
     rec_pass.release(); apply_nodes.release(); leaf_rec0.release(); leaf_start.release();
     kr_keys.release(); kr_idx.release(); kr_small.release();
-    bfs_a.release(); bfs_b.release(); bfs_mask.release(); bfs_ptr.release(); surf_color.release(); surf_tiles.release(); field_bits.release(); field_a.release(); field_b.release(); reach_bits.release(); reach_flags.release(); plan_bits.release(); plan_weights.release(); plan_ctl.release(); ground_bits.release(); ground_a.release(); ground_b.release(); ground_body.release(); ground_foot.release(); ground_ctl.release(); comp_bits.release(); comp_ctl.release(); near_bits.release(); near_dist.release(); near_arg.release(); vis_bits.release(); cov_bits.release(); cov_targets.release(); cov_matrix.release(); cov_state.release(); score_rec.release(); misc.release(); scan_tmp.release(); frame_bbox.release();
+    bfs_a.release(); bfs_b.release(); bfs_mask.release(); bfs_ptr.release(); surf_color.release(); surf_tiles.release(); field_bits.release(); field_a.release(); field_b.release(); reach_bits.release(); reach_flags.release(); plan_bits.release(); plan_weights.release(); plan_ctl.release(); ground_bits.release(); ground_a.release(); ground_b.release(); ground_body.release(); ground_foot.release(); ground_ctl.release(); comp_bits.release(); comp_ctl.release(); near_bits.release(); near_dist.release(); near_arg.release(); vis_bits.release(); cov_bits.release(); cov_targets.release(); cov_matrix.release(); cov_state.release(); obs_bits.release(); front_bits.release(); score_rec.release(); misc.release(); scan_tmp.release(); frame_bbox.release();
     if (h_counts) { (void)hipHostFree(h_counts); h_counts = nullptr; }
   }
 };
