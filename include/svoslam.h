@@ -821,6 +821,42 @@ int svoslam_pool_frontier_field(svoslam_workspace *ws, const svoslam_pool *pool,
  * only. */
 int svoslam_workspace_observe_buffers(const svoslam_workspace *ws, void *d_ptrs[1], uint64_t bytes[1]);
 int svoslam_workspace_frontier_buffers(const svoslam_workspace *ws, void *d_ptrs[1], uint64_t bytes[1]);
+/* The owner field of a map region (no reference counterpart; specification here and in DESIGN.md section 26): the reach field's
+ * steps and, for every reached cell, WHICH seed is nearest by path -- a partition of free space among seeds (robots sharing a
+ * frontier, the nearest dock, rooms grown back from their cores: `segment_rooms` of the Python package).  Exact, in integers.
+ *   d, N, the occupied set, the region and the traversable set T are exactly svoslam_pool_reach_field's: T = the region cells where
+ *     svoslam_pool_distance_field with radius_cells = clearance_cells writes -1.  Moves go to the six face neighbours, inside T
+ *     and inside the region.
+ *   Seeds, list form (d_seed_field == NULL): d_seeds, n_seeds triples (x, y, z) as in svoslam_pool_reach_field.  An entry counts
+ *     iff it lies in the region and in T; duplicates are allowed; the label of entry k is k.  n_seeds = 0 is allowed, and d_seeds
+ *     may then be NULL.
+ *   Seeds, field form (d_seed_field != NULL; d_seeds must then be NULL and n_seeds 0): d_seed_field is an int32 per region cell,
+ *     indexed as the outputs are.  A cell is a seed iff its value v satisfies 0 <= v < 2^31 - 1 and the cell is in T; its label is
+ *     v.  d_seed_field == d_owner is allowed, so a label field is grown in place: every cell's label is read before the cell is
+ *     written.  Any other overlap between arguments is the caller's error.
+ *   Outputs: d_steps and d_owner, each dims[0] * dims[1] * dims[2] values of type int32 in device memory, x fastest, indexed as
+ *     d_dist2 is.  d_steps is exactly what svoslam_pool_reach_field writes for the counted seeds: -2 not in T, -1 no path,
+ *     otherwise the shortest number of moves.  d_owner is, at a cell with steps >= 0, the SMALLEST LABEL AMONG THE COUNTED SEEDS
+ *     WHOSE SHORTEST PATH TO THE CELL HAS EXACTLY `steps` MOVES; elsewhere the value of d_steps (-1 or -2).  A seed cell that
+ *     carries several list entries takes the smallest index.  The tie rule is over all shortest paths, not the first to arrive:
+ *     the result does not depend on scheduling.  Only these values are specified, not how they are computed.
+ *   stats (may be NULL): seeds_used = the counted seed entries (list form, duplicates counted each) or seed cells (field form);
+ *     rounds, tile_runs (the steps' relaxation) and owner_rounds, owner_tile_runs (the owners') are diagnostics with no specified
+ *     value.
+ *   Conventions: those of svoslam_pool_reach_field -- pending asynchronous fusions are drained first; a deferred commit's pool is
+ *     read in its old state; THE CALL BLOCKS, with one 32-byte readback per round of either relaxation; one SVOSLAM_STAGE_QUERY
+ *     bracket around everything.  No slot of its own: d_steps and d_owner are the working arrays, the reach field's two slots hold
+ *     T's rows and the control record with the tile flags (one more int per tile than the reach field asks), so a second call of
+ *     the same size allocates nothing.
+ *   Errors: a zero entry of dims is SVOSLAM_OK and launches nothing, if the other arguments are valid.  SVOSLAM_ERR_INVALID_ARG:
+ *     those of svoslam_pool_reach_field; both seed forms given (d_seed_field with a non-NULL d_seeds or n_seeds != 0); with a
+ *     non-empty region a NULL d_steps or d_owner, or d_steps == d_owner.  SVOSLAM_ERR_POOL_LIMIT, SVOSLAM_ERR_OOM and
+ *     SVOSLAM_ERR_HIP: as svoslam_pool_reach_field, the limits decided before anything is allocated or written. */
+typedef struct { int32_t rounds, tile_runs, seeds_used, owner_rounds, owner_tile_runs; } svoslam_owner_stats;
+int svoslam_pool_owner_field(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                             const int32_t dims[3], int32_t clearance_cells, const int32_t *d_seeds, int32_t n_seeds,
+                             const int32_t *d_seed_field /* NULL: list form */, int32_t *d_steps, int32_t *d_owner,
+                             svoslam_owner_stats *stats /* may be NULL */, void *stream);
 /* Scoring candidate poses against a distance field (no reference counterpart; specification here and in DESIGN.md section 20): for
  * each of n_poses sensor-to-world matrices, move each of n sensor points by it, look the point's cell up in the field of a region
  * and add the values up -- the inner loop of a likelihood-field or chamfer relocaliser ("where in this map was this depth frame

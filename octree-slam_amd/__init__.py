@@ -50,6 +50,11 @@ class _ReachStats(C.Structure):
     _fields_ = [("rounds", C.c_int32), ("tile_runs", C.c_int32), ("seeds_used", C.c_int32)]
 
 
+class _OwnerStats(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("tile_runs", C.c_int32), ("seeds_used", C.c_int32), ("owner_rounds", C.c_int32),
+                ("owner_tile_runs", C.c_int32)]
+
+
 class _PlanStats(C.Structure):
     _fields_ = [("rounds", C.c_int32), ("tile_runs", C.c_int32), ("seeds_used", C.c_int32), ("max_weight", C.c_int32)]
 
@@ -219,6 +224,8 @@ SIGNATURES = {
     "svoslam_pool_reach_field": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _vp, _i32, _vp,
                                            C.POINTER(_ReachStats), _vp]),
     "svoslam_workspace_reach_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "svoslam_pool_owner_field": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _vp, _i32, _vp, _vp, _vp,
+                                           C.POINTER(_OwnerStats), _vp]),
     "svoslam_pool_label_components": (C.c_int, [_vp, C.POINTER(_PoolStruct), _i32, C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _vp, _vp,
                                                 C.POINTER(_ComponentStats), _vp]),
     "svoslam_workspace_component_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64)]),
@@ -1008,6 +1015,90 @@ def _cells_tensor(cells, what):
             raise ValueError("a %s tensor is int32 on the device" % what)
         return cells.reshape(-1, 3).contiguous()
     return torch.from_numpy(np.ascontiguousarray(np.asarray(cells, np.int32).reshape(-1, 3))).cuda()
+
+
+def owner_field(ws, pool, max_depth, origin, dims, clearance_cells, seeds=None, seed_field=None, as_tensor=False, stats=None, owner=None):
+    """svoslam_pool_owner_field: reach_field's steps and, with them, which seed is nearest by path.  Seeds are given one of two ways:
+    `seeds` ([n, 3] absolute cells: an array, or an int32 cuda tensor; the label of entry k is k), or `seed_field` (int32 [nz, ny,
+    nx]: an array or a cuda tensor; a traversable cell with a value 0 <= v < 2^31 - 1 is a seed with label v -- the labels of
+    label_components, say).  -> (steps, owner), int32 [nz, ny, nx] each: steps as reach_field gives them for the seeds that count
+    (-1 no path, -2 blocked); owner, at a cell with steps >= 0, the smallest label among the seeds whose shortest path to the cell
+    has exactly that many moves, elsewhere the value of steps.  numpy arrays, or with as_tensor cuda tensors.  `owner`: a
+    contiguous int32 cuda tensor of the region's shape that receives the owners; it may be the seed_field tensor itself, which is
+    then grown IN PLACE (otherwise a seed_field tensor is left as it is).  The call blocks either way.  `stats`: a dict that
+    receives rounds, tile_runs, seeds_used, owner_rounds and owner_tile_runs."""
+    import torch
+    o, n = [int(v) for v in origin], [int(v) for v in dims]
+    if len(o) != 3 or len(n) != 3:
+        raise ValueError("origin and dims are three cells each (x, y, z)")
+    if (seeds is None) == (seed_field is None):
+        raise ValueError("give the seeds as a list (seeds) or as a field of labels (seed_field), one of the two")
+    shape = [max(v, 0) for v in reversed(n)]
+    steps = torch.empty(shape, dtype=torch.int32, device="cuda")
+    if owner is None:
+        owner = torch.empty(shape, dtype=torch.int32, device="cuda")
+    elif not (isinstance(owner, torch.Tensor) and owner.is_cuda and owner.dtype == torch.int32 and owner.is_contiguous()
+              and list(owner.shape) == shape):
+        raise ValueError("owner is a contiguous int32 cuda tensor of the region's shape, [nz, ny, nx]")
+    if seed_field is None:
+        t_seeds = _cells_tensor(seeds, "seeds")
+        count = int(t_seeds.shape[0])
+        seed_args = (_ptr(t_seeds) if count else None, count, None)
+    else:
+        if isinstance(seed_field, torch.Tensor):
+            if not seed_field.is_cuda or seed_field.dtype != torch.int32:
+                raise ValueError("a seed_field tensor is int32 on the device")
+            t_field = seed_field if seed_field is owner else seed_field.contiguous()
+        else:
+            t_field = torch.from_numpy(np.ascontiguousarray(np.asarray(seed_field, np.int32))).cuda()
+        if list(t_field.shape) != shape:
+            raise ValueError("seed_field has the shape of the region, [nz, ny, nx]")
+        if not t_field.numel():                                         # no cell to point at; the pointer only says which form this is
+            t_field = torch.zeros(1, dtype=torch.int32, device="cuda")
+        seed_args = (None, 0, _ptr(t_field))
+    st = _OwnerStats()
+    check(lib().svoslam_pool_owner_field(ws._h, C.byref(pool._p), int(max_depth), (_i32 * 3)(*o), (_i32 * 3)(*n), int(clearance_cells),
+                                         *seed_args, _ptr(steps), _ptr(owner), C.byref(st), _stream()))
+    if stats is not None:
+        stats.update(rounds=int(st.rounds), tile_runs=int(st.tile_runs), seeds_used=int(st.seeds_used),
+                     owner_rounds=int(st.owner_rounds), owner_tile_runs=int(st.owner_tile_runs))
+    return (steps, owner) if as_tensor else (steps.cpu().numpy(), owner.cpu().numpy())
+
+
+def segment_rooms(ws, pool, max_depth, origin, dims, clearance_cells, door_cells, min_core=1):
+    """The rooms of a region, and the doors between them: free space is eroded to the cells at least door_cells clear of every
+    occupied cell, the components of what remains (label_components) are the cores, cores of fewer than min_core cells are dropped,
+    and owner_field grows every core back through the cells at least clearance_cells clear (door_cells >= clearance_cells): a cell
+    belongs to the core nearest by path, the smaller label on a tie.  Everything stays on the device until the end.  -> a dict of
+    numpy arrays: rooms int32 [nz, ny, nx] (a room's label is its core's smallest output index; -1 = free but reached by no core,
+    -2 = blocked), steps (moves to the room's core), cores (the seed field: the core's label, else -1), labels [k] ascending with
+    core_sizes [k] and room_sizes [k] in cells, and doors [m, 3] int64: (a, b, faces) for every pair a < b of room labels that are
+    face neighbours, faces the cell faces between them, sorted by (a, b)."""
+    import torch
+    if int(door_cells) < int(clearance_cells):
+        raise ValueError("door_cells is at least clearance_cells: a core is part of the space it grows back through")
+    cores, sizes = label_components(ws, pool, max_depth, origin, dims, int(door_cells), sizes=True, as_tensor=True)
+    cores = torch.where(sizes >= max(int(min_core), 1), cores, torch.full_like(cores, -1))
+    rooms = cores.clone()                                               # grown in place
+    steps, rooms = owner_field(ws, pool, max_depth, origin, dims, clearance_cells, seed_field=rooms, as_tensor=True, owner=rooms)
+    cells = rooms.numel()
+    # every kept core reaches itself, so the rooms' labels are the kept cores' labels
+    labels, room_sizes = torch.unique(rooms[rooms >= 0], return_counts=True)
+    core_sizes = torch.unique(cores[cores >= 0], return_counts=True)[1]
+    pairs = []
+    for axis in range(3):
+        if rooms.shape[axis] < 2:
+            continue
+        a, b = rooms.narrow(axis, 0, rooms.shape[axis] - 1).reshape(-1).long(), rooms.narrow(axis, 1, rooms.shape[axis] - 1).reshape(-1).long()
+        meet = (a >= 0) & (b >= 0) & (a != b)
+        a, b = a[meet], b[meet]
+        pairs.append(torch.minimum(a, b) * cells + torch.maximum(a, b))
+    doors = torch.zeros((0, 3), dtype=torch.int64, device=rooms.device)
+    if pairs:
+        keys, faces = torch.unique(torch.cat(pairs), return_counts=True)          # sorted: by a, then by b
+        doors = torch.stack([keys // max(cells, 1), keys % max(cells, 1), faces], 1)
+    return dict(rooms=rooms.cpu().numpy(), steps=steps.cpu().numpy(), cores=cores.cpu().numpy(), labels=labels.cpu().numpy().astype(np.int32),
+                core_sizes=core_sizes.cpu().numpy(), room_sizes=room_sizes.cpu().numpy(), doors=doors.cpu().numpy())
 
 
 def cost_field(ws, pool, max_depth, origin, dims, clearance_cells, comfort_cells, ring_cost, seeds, as_tensor=False, stats=None):

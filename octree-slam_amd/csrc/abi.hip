@@ -14,6 +14,7 @@
 #include "map_ground.hpp"
 #include "map_nearest.hpp"
 #include "map_observe.hpp"
+#include "map_owner.hpp"
 #include "map_paths.hpp"
 #include "map_plan.hpp"
 #include "map_query.hpp"
@@ -525,6 +526,14 @@ int svoslam_workspace_frontier_buffers(const svoslam_workspace *ws, void *d_ptrs
   d_ptrs[0] = ws->front_bits.ptr;
   bytes[0] = ws->front_bits.bytes;
   return SVOSLAM_OK;
+}
+
+int svoslam_pool_owner_field(svoslam_workspace *ws, const svoslam_pool *pool, int32_t max_depth, const int32_t origin_cell[3],
+                             const int32_t dims[3], int32_t clearance_cells, const int32_t *d_seeds, int32_t n_seeds,
+                             const int32_t *d_seed_field, int32_t *d_steps, int32_t *d_owner, svoslam_owner_stats *stats, void *stream) {
+  NEED_DEVICE();
+  return pool_owner_field(ws, pool, max_depth, origin_cell, dims, clearance_cells, d_seeds, n_seeds, d_seed_field, d_steps, d_owner, stats,
+                          S(stream));
 }
 
 int svoslam_score_poses(svoslam_workspace *ws, const int32_t *d_dist2, int32_t max_depth, const float center[3], float edge_length,

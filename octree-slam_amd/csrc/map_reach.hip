@@ -19,6 +19,8 @@
 //                       writes), with a barrier between sweeps; rows are at dword row * 66 + 1 + lane: 64 consecutive dwords per
 //                       access.  Passes repeat until one changes nothing (a workgroup-wide OR): every pass lowers a value or is the
 //                       last.
+// The host function is reach_relax with relax_seed as its seeding; the owner field (map_owner.hip) runs the same relaxation behind
+// a seeding of its own.
 // Resource report (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): reach_relax_kernel 56 VGPRs, 90 SGPRs, 27176 bytes of
 // static LDS (6 workgroups per CU of 160 KB), occupancy 6 by registers; 0 bytes of scratch.  No per-lane arrays indexed at run
 // time, no inline assembly.
@@ -84,40 +86,50 @@ __global__ __launch_bounds__(256) void reach_relax_kernel(int32_t *__restrict__ 
 
 }  // namespace
 
-int pool_reach_field(svoslam_workspace *ws, const svoslam_pool *pool, int depth, const int32_t origin[3], const int32_t dims[3],
-                     int32_t r, const int32_t *d_seeds, int32_t n_seeds, int32_t *d_steps, svoslam_reach_stats *stats,
-                     hipStream_t stream) {
-  const char *fn = "svoslam_pool_reach_field";
-  if (stats) stats->rounds = stats->tile_runs = stats->seeds_used = 0;
-  if (!ws || r < 0 || r > SVOSLAM_MAX_RADIUS_CELLS || n_seeds < 0 || (n_seeds > 0 && !d_seeds)) return SVOSLAM_ERR_INVALID_ARG;
-  RegionPlan own;  // the region itself: its row words are <= the field's own, within its limits
+int reach_relax(const char *fn, svoslam_workspace *ws, const svoslam_pool *pool, int depth, const int32_t origin[3],
+                const int32_t dims[3], int32_t r, int32_t *d_steps, int spare, const std::function<int(const ReachFrame &)> &seed,
+                AdoptedBracket &bracket, ReachFrame *frame, long long *rounds, RelaxControl *seen, hipStream_t stream) {
+  ReachFrame &f = *frame;
+  RegionPlan &own = f.own;  // the region itself: its row words are <= the field's own, within its limits
   SVO_TRY(plan_region(depth, origin, dims, 0, &own));
   if (own.nothing) return SVOSLAM_OK;
-  const TileGrid g = tile_grid(own.nx, own.ny, own.nz, own.nx, own.nx * own.ny, 1, own.ny, own.wpr);
-  const long long tiles = g.tiles();
+  const TileGrid g = f.g = tile_grid(own.nx, own.ny, own.nz, own.nx, own.nx * own.ny, 1, own.ny, own.wpr);
+  const long long tiles = f.tiles = g.tiles();
   // decided here, before anything is allocated or written
   if (own.n_out <= INT_MAX) SVO_TRY(relax_tile_limit(fn, g, own.ny, own.nz));
   // the traversable set, as the field's -1, in d_steps: the rest of the argument checks, the field's limits (decided before
   // anything is allocated), the drain of pending fusions and the field's own slots are pool_distance_field's
   SlotRollback grown(ws, &ws->reach_bits, &ws->reach_flags);
-  AdoptedBracket bracket(stream);
   SVO_TRY(pool_distance_field(ws, pool, depth, origin, dims, r, d_steps, nullptr, stream, &bracket.token));
   int rc = ws->reach_bits.reserve((size_t)own.words * 8);
-  if (rc == SVOSLAM_OK) rc = ws->reach_flags.reserve(kControlBytes + (size_t)tiles * 8);
+  if (rc == SVOSLAM_OK) rc = ws->reach_flags.reserve(kControlBytes + (size_t)tiles * 4 * (2 + spare));
   if (rc != SVOSLAM_OK) return grown.undo(rc, stream);
-  unsigned long long *bits = ws->reach_bits.as<unsigned long long>();
-  RelaxControl *ctl = ws->reach_flags.as<RelaxControl>();
-  int *flags = reinterpret_cast<int *>(ws->reach_flags.as<char>() + kControlBytes);
+  unsigned long long *bits = f.bits = ws->reach_bits.as<unsigned long long>();
+  RelaxControl *ctl = f.ctl = ws->reach_flags.as<RelaxControl>();
+  int *flags = f.flags = reinterpret_cast<int *>(ws->reach_flags.as<char>() + kControlBytes);
   SVO_HIP(hipMemsetAsync(ctl, 0, kControlBytes + (size_t)tiles * 8, stream));
   SVO_TRY(region_pack(own, d_steps, false, &kNone, bits, stream));  // d_steps becomes the working array in place
-  SVO_TRY(relax_seed(d_seeds, n_seeds, origin, g, bits, d_steps, flags, ctl, stream));
-  long long rounds;
-  RelaxControl seen;
+  SVO_TRY(seed(f));
   SVO_TRY(relax_rounds(fn, tiles, ctl, flags, stream, [&](int *now, int *next) {
     reach_relax_kernel<<<(unsigned)tiles, 256, 0, stream>>>(d_steps, bits, g, now, next, ctl);
-  }, &rounds, &seen));
+  }, rounds, seen));
   SVO_TRY(relax_finish(d_steps, own.nx, own.wpr, own.words, bits, stream));
-  if (stats) relax_stats(stats, rounds, seen);
+  return SVOSLAM_OK;
+}
+
+int pool_reach_field(svoslam_workspace *ws, const svoslam_pool *pool, int depth, const int32_t origin[3], const int32_t dims[3],
+                     int32_t r, const int32_t *d_seeds, int32_t n_seeds, int32_t *d_steps, svoslam_reach_stats *stats,
+                     hipStream_t stream) {
+  if (stats) stats->rounds = stats->tile_runs = stats->seeds_used = 0;
+  if (!ws || r < 0 || r > SVOSLAM_MAX_RADIUS_CELLS || n_seeds < 0 || (n_seeds > 0 && !d_seeds)) return SVOSLAM_ERR_INVALID_ARG;
+  AdoptedBracket bracket(stream);
+  ReachFrame frame;
+  long long rounds;
+  RelaxControl seen;
+  SVO_TRY(reach_relax("svoslam_pool_reach_field", ws, pool, depth, origin, dims, r, d_steps, 0, [&](const ReachFrame &f) {
+    return relax_seed(d_seeds, n_seeds, origin, f.g, f.bits, d_steps, f.flags, f.ctl, stream);
+  }, bracket, &frame, &rounds, &seen, stream));
+  if (stats && !frame.own.nothing) relax_stats(stats, rounds, seen);
   return SVOSLAM_OK;
 }
 

@@ -1,6 +1,6 @@
 // map_relax.hip -- what the tiled relaxations share beyond map_relax.hpp's inline pieces: the seed kernel of
 // the reach and cost fields, the finish kernel of all three fields, the tile limit, and the argument checks of the two trace
-// functions.  Resource report (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): relax_seed_kernel 12 VGPRs, relax_finish_kernel
+// functions.  Resource report (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): relax_seed_kernel 16 VGPRs, relax_finish_kernel
 // 14, no LDS, occupancy 8, 0 bytes of scratch.
 #include "map_relax.hpp"
 
@@ -18,7 +18,7 @@ __global__ __launch_bounds__(256) void relax_seed_kernel(const int32_t *__restri
   if (!((bits[(a * g.ba + b * g.bb) * g.wpr + (x >> 6)] >> (x & 63)) & 1ull)) return;
   store_value(values + a * g.sa + b * g.sb + x, 0);
   atomicAdd(&ctl->seeds_used, 1);
-  flags[((b / kTileB) * g.tiles_a + a / kTileA) * g.tiles_x + x / kTileX] = 1;
+  relax_mark_seed(flags, g, (int)x, (int)a, (int)b, (x & 63) == 0, (x & 63) == 63);
 }
 
 __global__ __launch_bounds__(256) void relax_finish_kernel(int32_t *__restrict__ values, int nx, int wpr, long long words,

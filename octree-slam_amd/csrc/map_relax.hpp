@@ -60,7 +60,7 @@ inline TileGrid tile_grid(long long nx, long long na, long long nb, long long sa
 // x nz cells, when the grid has more tiles than that
 int relax_tile_limit(const char *fn, const TileGrid &g, long long ny, long long nz);
 // one lane per seed entry (x, y, z; the grid's a = y, b = z): a seed in the region whose bit is set writes 0, is counted, and marks
-// its tile
+// its tile and the tiles that see it in their halo (relax_mark_seed)
 int relax_seed(const int32_t *d_seeds, int n_seeds, const int32_t origin[3], const TileGrid &g, const unsigned long long *bits,
                int32_t *values, int *flags, RelaxControl *ctl, hipStream_t stream);
 // "none" becomes -1, a cell without its bit -2
@@ -187,6 +187,22 @@ __device__ __forceinline__ void relax_count(int f, RelaxControl *__restrict__ ct
     if (f) atomicAdd(&ctl->changed_tiles, 1ull);
     atomicAdd(&ctl->tile_runs, 1ull);
   }
+}
+
+// Round 0's flags of a seed at cell (x, a, b) of a field whose moves go to face neighbours: its own tile, and the tile across every
+// tile face the cell lies on, where there is one (on_lo_x, on_hi_x: the cell is lane 0, lane 63 of its row word).  The write-back
+// raises flags for cells that FELL; a seed's own value is in place before the first round and never falls, so without this a seed
+// whose in-tile neighbours are all blocked would leave the tile that sees it in its halo asleep.
+__device__ __forceinline__ void relax_mark_seed(int *__restrict__ flags, const TileGrid &g, int x, int a, int b, bool on_lo_x, bool on_hi_x) {
+  const int tx = x / kTileX, ta = a / kTileA, tb = b / kTileB;
+  const int tile = (tb * g.tiles_a + ta) * g.tiles_x + tx;
+  flags[tile] = 1;
+  if (on_lo_x && tx > 0) flags[tile - 1] = 1;
+  if (on_hi_x && tx + 1 < g.tiles_x) flags[tile + 1] = 1;
+  if (a % kTileA == 0 && ta > 0) flags[tile - g.tiles_x] = 1;
+  if (a % kTileA == kTileA - 1 && ta + 1 < g.tiles_a) flags[tile + g.tiles_x] = 1;
+  if (b % kTileB == 0 && tb > 0) flags[tile - g.tiles_x * g.tiles_a] = 1;
+  if (b % kTileB == kTileB - 1 && tb + 1 < g.tiles_b) flags[tile + g.tiles_x * g.tiles_a] = 1;
 }
 
 // The rule of the fields whose moves go to face neighbours (reach, cost): a lowered cell on a face of the tile is seen by the
