@@ -49,4 +49,5 @@ from ._sensor import (  # noqa: F401
     image_load, focal_from_fov, FrameReader, generate_vertex_map, generate_vertex_map_rows, generate_normal_map, bilateral_filter,
     subsample_depth, subsample, color_to_intensity, transform_vertex_map, transform_normal_map, transform_vertex_map_dmat,
     point_cloud_bbox, point_cloud_bbox_device, gradient, difference, rgbd_cost, icp_cost2, icp_cost, icp_accumulate)
+from . import corridors  # noqa: F401
 from ._tracker import TRACK_FORM_NONE, TRACK_FORM_CHAIN, TRACK_FORM_ONE_LAUNCH, TRACK_FORM_STREAM, TRACK_FORM_HYBRID, Camera  # noqa: F401

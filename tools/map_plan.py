@@ -2,7 +2,7 @@
 
     python tools/map_plan.py CHECKPOINT OUT.npz --box x0 y0 z0 x1 y1 z1 --clearance CELLS --comfort CELLS
            (--penalty P | --ring-cost c1 c2 ...) --goal x y z --start x y z [--start ...] [--depth D]
-           [--straighten [--lookahead K]]
+           [--straighten [--lookahead K]] [--corridor EXTENT]
 
 The box (metres, min xyz then max xyz) becomes the cell range svoslam_pool_count_boxes would count (svoslam_box_to_cells) at depth D
 (default: the map's stored depth), and the goal and every --start (metres) the cell that holds it, by the same rule.
@@ -29,7 +29,17 @@ length^2 segment walks per path).  OUT.npz then also holds
   waypoints_K           int32 [k, 3], the cells at them, and waypoint_polyline_K float64 [k, 3], their centres in metres
   straight_lengths      float64 [n], the Euclidean length of each waypoint polyline in metres (0: no path), and lookahead
 
-Prints, per start, the cells and metres of its path and its cost, and with --straighten its waypoints and their metres."""
+With --corridor EXTENT every path also gets a safe corridor (svoslam_field_path_corridors): a chain of overlapping axis-aligned
+boxes of cells that are all more than --clearance cells from every occupied cell, each grown at most EXTENT (0 .. 65536) layers a
+direction from a cell of the path and its successor, judged on the distance field with the comfort radius.  OUT.npz then also holds
+
+  boxes_K               int32 [k, 6], the boxes of start K's path in cells, lo xyz then hi xyz, both inclusive
+  boxes_m_K             float64 [k, 6], the same in metres: the lo corner and the hi corner, the outer faces of the cubes
+  anchors_K             int32 [k], indices into cells_K: the cell each box was grown from; consecutive boxes share the next one's
+  corridor_gaps         int32 [n], the places where a path's chain is broken (0 for every path this tool traces), and corridor_extent
+
+Prints, per start, the cells and metres of its path and its cost, with --straighten its waypoints and their metres, and with
+--corridor its boxes."""
 import argparse
 import os
 import sys
@@ -55,7 +65,10 @@ def main():
     ap.add_argument("--depth", type=int, default=None, help="lattice depth (default: the stored depth)")
     ap.add_argument("--straighten", action="store_true", help="also prune every path into waypoints joined by straight segments")
     ap.add_argument("--lookahead", type=int, default=0, help="with --straighten: cells a waypoint looks ahead (0: the whole path)")
+    ap.add_argument("--corridor", type=int, default=None, metavar="EXTENT", help="also a chain of free boxes along every path, grown at most EXTENT layers a direction")
     args = ap.parse_args()
+    if args.corridor is not None and not 0 <= args.corridor <= 65536:
+        sys.exit("--corridor is 0 .. 65536")
     if args.lookahead and not args.straighten:
         sys.exit("--lookahead goes with --straighten")
     if args.lookahead < 0:
@@ -71,8 +84,12 @@ def main():
     pool, ws = pkg.Pool(), pkg.Workspace()
     center, edge, stored = pool.load(args.checkpoint)
     depth = stored if args.depth is None else args.depth
-    plan = pkg.plan_paths(ws, pool, depth, center, edge, args.box, args.goal, args.start, args.clearance, args.comfort, ring_cost,
-                          **(dict(straighten=True, max_lookahead=args.lookahead) if args.straighten else {}))
+    more = dict(straighten=True, max_lookahead=args.lookahead) if args.straighten else {}
+    if args.corridor is None:
+        plan = pkg.plan_paths(ws, pool, depth, center, edge, args.box, args.goal, args.start, args.clearance, args.comfort, ring_cost, **more)
+    else:
+        plan = pkg.corridors.plan_corridors(ws, pool, depth, center, edge, args.box, args.goal, args.start, args.clearance, args.comfort,
+                                            ring_cost, args.corridor, **more)
     if plan is None:
         sys.exit("the box is empty: a NaN, min > max, or outside the root cube")
     none = np.full(3, -1, np.int32)
@@ -95,6 +112,13 @@ def main():
             out["vertices_%d" % k] = p["vertices"] if p["vertices"] is not None else np.zeros(0, np.int32)
             out["waypoints_%d" % k] = p["waypoints"] if p["waypoints"] is not None else np.zeros((0, 3), np.int32)
             out["waypoint_polyline_%d" % k] = p["waypoint_polyline"] if p["waypoint_polyline"] is not None else np.zeros((0, 3), np.float64)
+    if args.corridor is not None:
+        out["corridor_extent"] = args.corridor
+        out["corridor_gaps"] = np.array([p["gaps"] or 0 for p in paths], np.int32)
+        for k, p in enumerate(paths):
+            out["boxes_%d" % k] = p["boxes"] if p["boxes"] is not None else np.zeros((0, 6), np.int32)
+            out["boxes_m_%d" % k] = p["boxes_m"] if p["boxes_m"] is not None else np.zeros((0, 6), np.float64)
+            out["anchors_%d" % k] = p["anchors"] if p["anchors"] is not None else np.zeros(0, np.int32)
     np.savez_compressed(args.out, **out)
     print("depth %d, cells %s + %s, clearance %d, comfort %d, ring cost %s -> %s" % (
         depth, plan["origin"].tolist(), plan["dims"].tolist(), args.clearance, args.comfort, ring_cost, args.out))
@@ -105,6 +129,8 @@ def main():
             print("start %d: %d cells, %.3f m, cost %d" % (k, p["length"], (p["length"] - 1) * plan["cell_size"], p["cost"]))
             if args.straighten:
                 print("start %d: %d waypoints, %.3f m" % (k, len(p["vertices"]), p["straight_length"]))
+            if args.corridor is not None:
+                print("start %d: %d boxes, %d gaps" % (k, len(p["boxes"]), p["gaps"]))
 
 
 if __name__ == "__main__":
